@@ -9,6 +9,11 @@ Weights / KV cache are resident in HBM before the timed region.  N > 1: N indepe
 process per GPU, no data-path collective -- decode of one sequence does not shard).
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps decode steps and prints the line.  --full adds every secondary
+measurement (kernel roofline, extras, pp512 / TTFT, C3 prefill, the reference-harness legs, --omni-pinned, the
+CPU baseline).  --dump-outputs DIR writes the logits of the last timed step as DIR/logits.npy (float32); the
+inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import importlib.util
@@ -878,7 +883,14 @@ def main():
     ap.add_argument("--omni-pinned", action="store_true", help="add `omni_pinned`: C4 TTFT / C5 chunk measured with every module on its mi355x_module_device() backend and real hand-offs")
     ap.add_argument("--no-omni-runtime", action="store_true", help="skip the via_reference_omni_runtime leg (the reference's omni.cpp driving the plug-in; ~60 s)")
     ap.add_argument("--no-libllama", action="store_true", help="skip the via_libllama leg (the metric through the reference's libllama with this plug-in)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements (roofline, extras, pp512, C3, reference-harness legs, "
+                    "--omni-pinned, CPU baseline); the --no-* / --c3 / --omni-pinned options select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the logits of the last timed step to DIR/logits.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.c3 or args.omni_pinned) and not args.full:
+        ap.error("--c3 and --omni-pinned select legs of --full: add --full")
 
     if args.cpu_baseline_only or args.cpu_baseline_worker:
         pkg = load_pkg()
@@ -903,13 +915,17 @@ def main():
     wbytes = dec.model.weight_bytes()
 
     dt, pos = rep.timed(dec.step, args.steps, args.warmup, be.synchronize)
+    last_logits = np.array(dec.h_logits, dtype=np.float32, copy=True)    # what llama_decode hands its caller after the last timed step
     evidence = rep.evidence(args.steps, rep.dt_local)              # (a collective: every rank takes part)
     replays = be.get_stat("graph_replays")
     kernels = be.get_stat("kernels_last_graph")
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), last_logits)
 
     # ---- dominant kernel, measured live: replay of exactly the step's Q4_K mat-vec launches with HIP events at both ends
     roof = None
-    if rank == 0 and not args.tiny:                               # (the tiny plumbing config is below the batch-1 kernels' shapes: no roofline)
+    if args.full and rank == 0 and not args.tiny:                 # (the tiny plumbing config is below the batch-1 kernels' shapes: no roofline)
         roof = kernel_roofline(pkg, be, dec.model)
         if os.environ.get("MI355X_BENCH_PROFILE"):
             be.set_option("profile", 1)
@@ -943,9 +959,9 @@ def main():
         }
         if evidence:
             out.update(evidence)
-        if world == 1 and not args.tiny and not os.environ.get("MI355X_BENCH_NO_EXTRAS"):
+        if args.full and world == 1 and not args.tiny and not os.environ.get("MI355X_BENCH_NO_EXTRAS"):
             out["extras"] = extra_legs(pkg, be, args.no_fa)        # (before the prefill legs: they leave 15 GB of F16 weight images behind)
-        if world == 1 and not os.environ.get("MI355X_BENCH_NO_PP"):
+        if args.full and world == 1 and not os.environ.get("MI355X_BENCH_NO_PP"):
             try:                                                   # second half of the headline metric: pp512 (reported, not `value`)
                 pp, ok = prefill_tok_s(pkg, be, dec.model)
                 out["pp512_tok_s"] = round(pp, 1) if ok else None
@@ -975,13 +991,13 @@ def main():
             except Exception as e:
                 out["pp512_tok_s"] = None
                 out["pp512_error"] = repr(e)
-        if (args.c3 or not (args.no_c3 or args.tiny)) and world == 1:
+        if args.full and (args.c3 or not (args.no_c3 or args.tiny)) and world == 1:
             try:
                 out["c3_f16_prefill"] = {"ub512": c3_prefill(pkg, be, n_ubatch=512, tiny=args.tiny), "ub2048": c3_prefill(pkg, be, n_ubatch=2048, tiny=args.tiny),
                                         "ub16384": c3_prefill(pkg, be, tiny=args.tiny, one_ubatch=True)}
             except Exception as e:
                 out["c3_f16_prefill"] = {"error": repr(e)}
-        if world == 1 and not args.tiny and not args.no_libllama and not os.environ.get("MI355X_BENCH_NO_EXTRAS"):
+        if args.full and world == 1 and not args.tiny and not args.no_libllama and not os.environ.get("MI355X_BENCH_NO_EXTRAS"):
             be.synchronize()
             out["via_reference_omni_modules"] = via_reference_omni_modules()
             if not args.no_omni_runtime:
@@ -995,10 +1011,10 @@ def main():
             if v and isinstance(v.get("fa0"), dict):
                 out["value_via_libllama"] = v["fa0"].get("tg128_tok_s")
                 out["pp512_via_libllama"] = v["fa0"].get("pp512_tok_s")
-        if args.omni_pinned and world == 1 and not args.tiny:
+        if args.full and args.omni_pinned and world == 1 and not args.tiny:
             be.synchronize()
             out["omni_pinned"] = omni_pinned(pkg, be, dec.model)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(pkg, cfg, types, n_kv, tiny=args.tiny)
         else:
             out["cpu_baseline"] = None

@@ -522,6 +522,28 @@ def test_bench_runs_as_two_ranks_through_its_gloo_hooks(tmp_path):
     assert abs(j["value"] - 2 * 8 / (j["ms_per_step"] * 8 / 1e3)) / j["value"] < 1e-3       # aggregate = ranks x steps / max-over-ranks time
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step_logits(tmp_path):
+    """bench.py without --full times exactly --steps decode steps and runs none of the secondary legs; --dump-outputs writes the logits of the
+    last timed step, and two runs with the same arguments (seeded inputs) give the same logits."""
+    outs = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--tiny", "--dump-outputs", d],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 6 and j["warmup"] == 2 and j["ms_per_step"] > 0
+        assert abs(j["value"] - 1e3 / j["ms_per_step"]) / j["value"] < 1e-3
+        assert j["roofline"] is None and j["cpu_baseline"] is None
+        assert not {"extras", "pp512_tok_s", "c3_f16_prefill", "via_libllama", "omni_pinned"} & set(j), sorted(j)
+        logits = np.load(os.path.join(d, "logits.npy"))
+        assert logits.dtype == np.float32 and logits.shape == (j["config"]["n_vocab"],) and np.isfinite(logits).all() and logits.std() > 0
+        outs.append(logits)
+    assert nmse(outs[1], outs[0]) < 1e-10, nmse(outs[1], outs[0])
+
+
 def test_gate_up_swiglu_in_the_gemm_epilogue_vs_oracle(pkg, be):
     """ffn_up / ffn_gate -> SWIGLU -> ffn_down at a prefill shape: the two mat-muls and the GLU become ONE launch of k_gemm_f16_ph8<GLU> (W-h0 from
     the gate matrix, W-h1 from the up matrix, silu(gate) * up rounded to f16 in the epilogue -- the activation image of ffn_down); the

@@ -376,7 +376,7 @@ def test_bench_omni_pinned_mode_measures_c4_and_c5_with_real_handoffs():
     hand-off really went through the library (kind 1 = RCCL, 2 = device copy + event), and the concurrent APM / VPM submission does not take longer
     than the legs one after the other."""
     env = dict(os.environ, MI355X_BENCH_NO_PP="1", MI355X_BENCH_NO_EXTRAS="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "4", "--no-cpu-baseline", "--no-c3", "--no-libllama", "--omni-pinned"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "4", "--full", "--no-cpu-baseline", "--no-c3", "--no-libllama", "--omni-pinned"],
                          env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,7 +1,7 @@
 """tools/host_overhead.py -- where a decode step's wall time goes on the host side: time inside graph_compute (fingerprint + hipGraphLaunch,
 asynchronous), the uploads, and the wait for the device."""
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 pkg = bench.load_pkg()
 from llama_cpp_omni_amd import qwen3

@@ -20,7 +20,7 @@ if os.path.exists("gpurun_out/bench_default.json"):
     shutil.copy("gpurun_out/bench_default.json", "profiles/" + TAG + "_bench.json")
 rows = list(csv.DictReader(open(stats)))
 with open("profiles/" + TAG + "_kernel_stats_summary.txt", "w") as f:
-    f.write("rocprofv3 --kernel-trace --stats --output-format csv -- MI355X_GRAPHS=0 python bench.py --steps 32 --warmup 8 --no-cpu-baseline\n")
+    f.write("rocprofv3 --kernel-trace --stats --output-format csv -- MI355X_GRAPHS=0 python bench.py --steps 32 --warmup 8 --full --no-cpu-baseline\n")
     f.write("(decode steps + the roofline replay + the extras [no-FA decode, TTS decoder, omni encoder / Token2Wav graphs] + the pp512 leg; graph replay off under the profiler)  tools/profile_round.sh\n\n")
     f.write("%-100s %8s %12s %8s\n" % ("kernel", "calls", "avg_ns", "pct"))
     for r in rows:
@@ -31,7 +31,7 @@ for r in csv.DictReader(open(pmc)):
         continue
     agg[r["Kernel_Name"]][0] += 1
     agg[r["Kernel_Name"]][1] += float(r["Counter_Value"])
-out = {"command": "MI355X_GRAPHS=0 MI355X_BENCH_NO_PP=1 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline",
+out = {"command": "MI355X_GRAPHS=0 MI355X_BENCH_NO_PP=1 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -- python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline",
        "unit_note": "FETCH_SIZE is reported in KiB and counts 64 B per 128-B request for wide coalesced streaming reads on gfx950: bytes = KiB * 1024 * 2 (MI355X_MICROARCH.md, HBM section)",
        "commit": COMMIT, "kernels": {}}
 for k, (n, v) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
