@@ -27,6 +27,8 @@ static inline type_info type_traits(int t) {
         case GGML_TYPE_Q5_K: return {256, 176, "q5_K"};
         case GGML_TYPE_Q6_K: return {256, 210, "q6_K"};
         case GGML_TYPE_Q8_K: return {256, 292, "q8_K"};
+        case GGML_TYPE_IQ4_NL: return {32, 18, "iq4_nl"};
+        case GGML_TYPE_IQ4_XS: return {256, 136, "iq4_xs"};
         case GGML_TYPE_I8:   return {1, 1, "i8"};
         case GGML_TYPE_I16:  return {1, 2, "i16"};
         case GGML_TYPE_I32:  return {1, 4, "i32"};

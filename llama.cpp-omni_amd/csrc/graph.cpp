@@ -402,6 +402,8 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "fattn_dma_launches")) return (double) mi::fattn_dma_launches();
     if (!strcmp(key, "fattn_gs_launches"))  return (double) mi::fattn_gs_launches();
     if (!strcmp(key, "fattn_gs_far_launches")) return (double) mi::fattn_gs_far_launches();
+    if (!strcmp(key, "mmv_iq4nl_launches")) return (double) mi::mmv_iq4_launches(false);
+    if (!strcmp(key, "mmv_iq4xs_launches")) return (double) mi::mmv_iq4_launches(true);
     if (!strncmp(key, "prof_", 5)) {
         std::string k(key + 5);
         const size_t us = k.rfind("_us"), nn = k.rfind("_n"), by = k.rfind("_bytes");

@@ -51,7 +51,8 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
 }
 
 const char * mmv_class(int type) {
-    return type == GGML_TYPE_Q4_K ? "mmv_q4k" : type == GGML_TYPE_Q6_K ? "mmv_q6k" : type == GGML_TYPE_Q8_0 ? "mmv_q80" : type == GGML_TYPE_F16 ? "mmv_f16" : "mmv_f32";
+    return type == GGML_TYPE_Q4_K ? "mmv_q4k" : type == GGML_TYPE_Q6_K ? "mmv_q6k" : type == GGML_TYPE_Q8_0 ? "mmv_q80" : type == GGML_TYPE_F16 ? "mmv_f16" :
+           type == GGML_TYPE_IQ4_NL ? "mmv_iq4nl" : type == GGML_TYPE_IQ4_XS ? "mmv_iq4xs" : "mmv_f32";
 }
 
 // resident F16 image of a quantised weight matrix (shadow.hpp): built on first use outside of graph capture, only for tensors
@@ -268,6 +269,8 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out
                     case GGML_TYPE_Q8_0: mmv_q8_0(a, s.st); break;
                     case GGML_TYPE_Q4_0: mmv_q4_0(a, s.st); break;
                     case GGML_TYPE_Q5_0: mmv_q5_0(a, s.st); break;
+                    case GGML_TYPE_IQ4_NL: mmv_iq4_nl(a, s.st); break;
+                    case GGML_TYPE_IQ4_XS: mmv_iq4_xs(a, s.st); break;
                     case GGML_TYPE_F16:  mmv_f16(a, s.st); break;
                     default:             mmv_f32(a, s.st); break;
                 }

@@ -32,11 +32,14 @@ static inline bool is_image_quant(int t) {
 }
 // Q4_0 / Q5_0: integer mat-vec kernels on Q8_0 activations up to 8 columns (mmvq.hip), the F16 image from 9 columns on
 static inline bool is_q40_like(int t) { return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q5_0; }
+// IQ4_NL / IQ4_XS: integer mat-vec kernels up to 8 columns (mmvq.hip: IQ4_NL on Q8_0 images, IQ4_XS on Q8_K images), the F16 image from 9 columns on.
+// IQ4_XS shares the Q8_K image with the K-quants, but none of the K-quant launch forms (fusions, mmq, the k_mv2 engine) takes it: those test is_kquant / the type.
+static inline bool is_iq4(int t) { return t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_IQ4_XS; }
 static inline act_kind act_kind_for(int wtype) {
     if (is_image_quant(wtype)) return ACT_F16;
     switch (wtype) {
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: return ACT_Q8K;
-        case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q5_0: return ACT_Q80;
+        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_IQ4_XS: return ACT_Q8K;
+        case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q5_0: case GGML_TYPE_IQ4_NL: return ACT_Q80;
         case GGML_TYPE_F16:  return ACT_F16;
         case GGML_TYPE_F32:  return ACT_F32;
         default: return ACT_NONE;

@@ -39,6 +39,9 @@ void mmv_q5_K(const mmv_args & a, hipStream_t st);
 void mmv_q8_0(const mmv_args & a, hipStream_t st);
 void mmv_q4_0(const mmv_args & a, hipStream_t st);   // Q4_0 / Q5_0 weights x Q8_0 activation images (the reference's vec_dot_q4_0_q8_0 / _q5_0_q8_0 integers)
 void mmv_q5_0(const mmv_args & a, hipStream_t st);
+void mmv_iq4_nl(const mmv_args & a, hipStream_t st);  // IQ4_NL x Q8_0 images / IQ4_XS x Q8_K images (vec_dot_iq4_nl_q8_0 / _iq4_xs_q8_K integers; K % 32 / K % 256 == 0)
+void mmv_iq4_xs(const mmv_args & a, hipStream_t st);
+long mmv_iq4_launches(bool xs);                       // kernel launches so far (stat "mmv_iq4nl_launches" / "mmv_iq4xs_launches")
 void mmv_f16 (const mmv_args & a, hipStream_t st);   // act = f16 rows
 void mmv_f32 (const mmv_args & a, hipStream_t st);   // W f32, act = f32 rows
 

@@ -91,10 +91,11 @@ __global__ void __launch_bounds__(256) k_dequant_q80(const char * __restrict__ s
     (void) nb;
 }
 
-// ---- the other block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q5_K): one element at a time, the float operations of
-// dequantize_row_q4_0 :307, _q4_1 :327, _q5_0 :348, _q5_1 :374, _q2_K :784, _q3_K :1128, _q5_K :1554 (ggml-quants.c) in the same order.
+// ---- the other block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q5_K / IQ4_NL / IQ4_XS): one element at a time, the float operations of
+// dequantize_row_q4_0 :307, _q4_1 :327, _q5_0 :348, _q5_1 :374, _q2_K :784, _q3_K :1128, _q5_K :1554, _iq4_nl :2512, _iq4_xs :2530 (ggml-quants.c) in the same order.
 // These types have no integer-dot kernels here: MUL_MAT runs on their (resident) F16 image, GET_ROWS gathers through this function.
 static __device__ __forceinline__ float h2f_at(const uint8_t * p) { return h2f((uint16_t) (p[0] | (p[1] << 8))); }
+__constant__ int8_t kvalues_iq4nl_dev[16] = { -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 };     // ggml-common.h:1088-1090
 static __device__ float dq_elem_other(int type, const char * row, int64_t e) {
     switch (type) {
         case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: {
@@ -149,6 +150,21 @@ static __device__ float dq_elem_other(int type, const char * row, int64_t e) {
             const int hb = (b[16 + l] & ((hi ? 2 : 1) << (2 * p))) ? 16 : 0;
             return d1 * (float) (nib + hb) - m1;
         }
+        case GGML_TYPE_IQ4_NL: {                                      // d qs[16]: d * kvalues_iq4nl[q] (dequantize_row_iq4_nl :2512)
+            const uint8_t * b = (const uint8_t *) row + (e / 32) * 18;
+            const int w = (int) (e % 32);
+            const uint8_t q = b[2 + (w & 15)];
+            return h2f_at(b) * (float) kvalues_iq4nl_dev[w < 16 ? (q & 0xF) : (q >> 4)];
+        }
+        case GGML_TYPE_IQ4_XS: {                                      // d scales_h scales_l[4] qs[128]: (d * (ls - 32)) * kvalues_iq4nl[q] (dequantize_row_iq4_xs :2530)
+            const uint8_t * b = (const uint8_t *) row + (e / 256) * 136;
+            const int w = (int) (e % 256), ib = w >> 5, l = w & 31;
+            const int scales_h = b[2] | (b[3] << 8);
+            const int ls = ((b[4 + ib / 2] >> (4 * (ib % 2))) & 0xF) | (((scales_h >> (2 * ib)) & 3) << 4);
+            const float dl = h2f_at(b) * (float) (ls - 32);
+            const uint8_t q = b[8 + 16 * ib + (l & 15)];
+            return dl * (float) kvalues_iq4nl_dev[l < 16 ? (q & 0xF) : (q >> 4)];
+        }
         default: return 0.0f;
     }
 }
@@ -171,7 +187,7 @@ static void dequant_rows_t(int type, const void * src, size_t src_rs, T * dst, s
             k_dequant_q6k<T><<<dim3((unsigned) ((nthreads + 255) / 256)), dim3(256), 0, st>>>((const char *) src, src_rs, (char *) dst, dst_rs, K, nrows); break;
         case GGML_TYPE_Q8_0: nthreads = nrows * K;
             k_dequant_q80<T><<<dim3((unsigned) ((nthreads + 255) / 256)), dim3(256), 0, st>>>((const char *) src, src_rs, (char *) dst, dst_rs, K, nrows); break;
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K:
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS:
             nthreads = nrows * K;
             k_dequant_other<T><<<dim3((unsigned) ((nthreads + 255) / 256)), dim3(256), 0, st>>>(type, (const char *) src, src_rs, (char *) dst, dst_rs, K, nrows); break;
         default: fprintf(stderr, "[mi355x] dequant_rows: unsupported type %d\n", type); abort();
@@ -1256,7 +1272,7 @@ void get_rows(const tdesc & src, int src_type, const tdesc & idx, const tdesc & 
         case GGML_TYPE_F16: k_get_rows<uint16_t><<<grid, dim3(256), 0, st>>>(s, i, d); break;
         case GGML_TYPE_BF16: k_get_rows<bf16_t><<<grid, dim3(256), 0, st>>>(s, i, d); break;
         case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_K: case GGML_TYPE_Q6_K:
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K:
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS:
             k_get_rows_q<<<grid, dim3(256), 0, st>>>(src_type, s, i, d); break;
         default: fprintf(stderr, "[mi355x] get_rows: unsupported type %d\n", src_type); abort();
     }

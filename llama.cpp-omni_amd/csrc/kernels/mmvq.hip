@@ -1,4 +1,4 @@
-// mmvq.hip -- weight-streaming mat-vec kernels for Q8_0 / F16 / F32 weights (gfx950, wave64); the K-quants live in mmvk.hip.
+// mmvq.hip -- weight-streaming mat-vec kernels for Q8_0 / Q4_0 / Q5_0 / IQ4_NL / IQ4_XS / F16 / F32 weights (gfx950, wave64); the K-quants live in mmvk.hip.
 //
 // Computes what the reference CPU backend computes in ggml_compute_forward_mul_mat
 // (ggml-cpu/ggml-cpu.c:1210-1402) for ne11 <= 8: every output is one `vec_dot` of a quantised weight
@@ -219,6 +219,226 @@ __global__ void __launch_bounds__(256) k_mmv_q40(const char * __restrict__ W, si
                     const float t = (float) isum * (dx[r] * yd);
                     acc[r][c] += rv ? t : 0.0f;
                 }
+            }
+        }
+        if (cit == nit - 1) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int row = cgrp * ROWS + r;
+#pragma unroll
+                for (int c = 0; c < NCOLS; ++c) {
+                    const float s = wave_sum(acc[r][c]);
+                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
+                    acc[r][c] = 0.0f;
+                }
+            }
+        }
+        if (!more) break;
+    }
+}
+
+// =================================================================================================
+// IQ4_NL / IQ4_XS: 4-bit indices into the 16-entry int8 table kvalues_iq4nl (ggml-common.h:1088-1090), no min term.
+//   IQ4_NL x Q8_0 : ggml_vec_dot_iq4_nl_q8_0 (ggml-cpu/arch/x86/quants.c:3631; generic ggml-cpu/quants.c:1108-1131)
+//                   sumi = sum_j y.qs[j] * kv[x.qs[j] & 0xF] + y.qs[j + 16] * kv[x.qs[j] >> 4];  sumf += sumi * (d_x * d_y)
+//   IQ4_XS x Q8_K : ggml_vec_dot_iq4_xs_q8_K (x86 :3715; generic :1133-1170) -- the x86 form scales every 32-weight sub-block sum by
+//                   (ls - 32) in integers and converts once per 256-weight super-block: sumi = sum_ib (ls_ib - 32) * sumi_ib;  sumf += sumi * (d_x * d_y)
+// The table lives in four dwords of registers; four indices become four int8 values through two byte permutes (v_perm_b32 over the low
+// and the high 8-byte half of the table) and a per-byte select on the index's bit 3 (v_bfi_b32), then go straight into v_dot4_i32_i8.
+// =================================================================================================
+static __device__ __forceinline__ uint32_t iq4nl_lut4(uint32_t n) {      // n: four indices, one in the low nibble of each byte (upper nibbles zero)
+    const uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u;   // -127 -104 -83 -65 | -49 -35 -22 -10 | 1 13 25 38 | 53 69 89 113
+    const uint32_t i  = n & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(T1, T0, i);                 // selector byte k < 4: byte k of T0, 4..7: byte k - 4 of T1
+    const uint32_t hi = __builtin_amdgcn_perm(T3, T2, i);
+    uint32_t m = (n >> 3) & 0x01010101u;
+    m = (m << 8) - m;                                                     // 0xFF in every byte whose index is >= 8 (no borrow crosses a byte)
+    return (hi & m) | (lo & ~m);
+}
+
+// IQ4_NL: 18-B block {f16 d, qs[16]} (2-byte aligned).  Two lanes per block as k_mmv_q40: lane half hf owns qs bytes 8hf .. 8hf+7 = weights
+// 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high); 32 blocks per wave step, U steps per stage, next stage requested before the current
+// one is consumed.
+template <int NCOLS, int ROWS>
+__global__ void __launch_bounds__(256) k_mmv_iq4nl(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
+                                                  char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+    typedef u32x2 __attribute__((aligned(2))) u32x2a2;
+    constexpr int U = NCOLS <= 2 ? 2 : 1;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 1, hf = lane & 1;
+    const int nb  = K >> 5;
+    const int nit = (nb + 32 * U - 1) / (32 * U);
+    const size_t img = q80_image_bytes(K);
+    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * 4;
+    const int ngrp   = (nrows + ROWS - 1) / ROWS;
+
+    u32x2 q[U][ROWS]; uint32_t dw[U][ROWS];
+    auto issue = [&](int grp, int it) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int ib = (it * U + u) * 32 + g; ib = ib < nb ? ib : nb - 1;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
+                const char * bp = W + (size_t) row * w_rs + (size_t) ib * 18;
+                dw[u][r] = *(const uint16_t *) bp;
+                q[u][r]  = *(const u32x2a2 *) (bp + 2 + 8 * hf);
+            }
+        }
+    };
+    int grp = wave, it = 0;
+    if (grp < ngrp) issue(grp, 0);
+    stage_act(act, act_cs, NCOLS, img);
+    __syncthreads();
+    if (grp >= ngrp) return;
+
+    float acc[ROWS][NCOLS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
+    while (true) {
+        u32x2 cq[U][ROWS]; uint32_t cd[U][ROWS];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) { cq[u][r] = q[u][r]; cd[u][r] = dw[u][r]; }
+        const int cgrp = grp, cit = it;
+        ++it;
+        if (it == nit) { it = 0; grp += nwaves; }
+        const bool more = grp < ngrp;
+        if (more) issue(grp, it);
+
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int  ib    = (cit * U + u) * 32 + g;
+            const bool valid = ib < nb;
+            const int  ibc   = valid ? ib : nb - 1;
+            uint32_t lo[ROWS][2], hi[ROWS][2]; float dx[ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                dx[r] = h2f((uint16_t) cd[u][r]);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) { lo[r][k] = iq4nl_lut4(cq[u][r][k] & 0x0f0f0f0fu); hi[r][k] = iq4nl_lut4((cq[u][r][k] >> 4) & 0x0f0f0f0fu); }
+            }
+#pragma unroll
+            for (int c = 0; c < NCOLS; ++c) {
+                const char * im = mmv_lds + c * img;
+                const u32x2 a0 = *(const u32x2 *) (im + ibc * 32 + 8 * hf);
+                const u32x2 a1 = *(const u32x2 *) (im + ibc * 32 + 16 + 8 * hf);
+                const float yd = *(const float *) (im + K + ibc * 4);
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    const bool rv = valid && (cgrp * ROWS + r) < nrows;
+                    const int isum = dot4(lo[r][0], a0[0], dot4(lo[r][1], a0[1], dot4(hi[r][0], a1[0], dot4(hi[r][1], a1[1], 0))));
+                    const float t = (float) isum * (dx[r] * yd);
+                    acc[r][c] += rv ? t : 0.0f;
+                }
+            }
+        }
+        if (cit == nit - 1) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int row = cgrp * ROWS + r;
+#pragma unroll
+                for (int c = 0; c < NCOLS; ++c) {
+                    const float s = wave_sum(acc[r][c]);
+                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
+                    acc[r][c] = 0.0f;
+                }
+            }
+        }
+        if (!more) break;
+    }
+}
+
+// IQ4_XS: 136-B super-block {f16 d, u16 scales_h, u8 scales_l[4], qs[128]} (2-byte aligned rows), Q8_K image (mmv_lds: qs[K] | bsums | d[K/256]).
+// Four lanes per super-block: lane quarter qq owns the 32-weight sub-blocks 2qq and 2qq+1 (qs bytes 32qq .. 32qq+31, two 16-byte loads) and
+// reads the 8-byte header beside them; 16 super-blocks per wave step (K = 4096: one step per row), the next row group's loads issued before
+// the current one is consumed.  ls = scales_l nibble | two bits of scales_h << 4 (dequantize_row_iq4_xs, ggml-quants.c:2530-2550).
+template <int NCOLS, int ROWS>
+__global__ void __launch_bounds__(256) k_mmv_iq4xs(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
+                                                  char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+    typedef u32x2 __attribute__((aligned(2))) u32x2a2;
+    typedef u32x4 __attribute__((aligned(2))) u32x4a2;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 2, qq = lane & 3;
+    const int nb  = K >> 8;
+    const int nit = (nb + 15) / 16;
+    const size_t img = q8k_image_bytes(K);
+    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * 4;
+    const int ngrp   = (nrows + ROWS - 1) / ROWS;
+
+    u32x2 h[ROWS]; u32x4 q[ROWS][2];
+    auto issue = [&](int grp, int it) {
+        int ib = it * 16 + g; ib = ib < nb ? ib : nb - 1;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
+            const char * bp = W + (size_t) row * w_rs + (size_t) ib * 136;
+            h[r]    = *(const u32x2a2 *) bp;
+            q[r][0] = *(const u32x4a2 *) (bp + 8 + 32 * qq);
+            q[r][1] = *(const u32x4a2 *) (bp + 24 + 32 * qq);
+        }
+    };
+    int grp = wave, it = 0;
+    if (grp < ngrp) issue(grp, 0);
+    stage_act(act, act_cs, NCOLS, img);
+    __syncthreads();
+    if (grp >= ngrp) return;
+
+    float acc[ROWS][NCOLS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
+    while (true) {
+        u32x2 ch[ROWS]; u32x4 cq[ROWS][2];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) { ch[r] = h[r]; cq[r][0] = q[r][0]; cq[r][1] = q[r][1]; }
+        const int cgrp = grp, cit = it;
+        ++it;
+        if (it == nit) { it = 0; grp += nwaves; }
+        const bool more = grp < ngrp;
+        if (more) issue(grp, it);
+
+        const int  ib    = cit * 16 + g;
+        const bool valid = ib < nb;
+        const int  ibc   = valid ? ib : nb - 1;
+        uint32_t lo[ROWS][2][4], hi[ROWS][2][4]; int ls[ROWS][2]; float dx[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            dx[r] = h2f((uint16_t) (ch[r][0] & 0xffffu));
+            const uint32_t sh = (ch[r][0] >> 16) >> (4 * qq), sl = (ch[r][1] >> (8 * qq)) & 0xffu;
+            ls[r][0] = (int) ((sl & 0xfu) | ((sh & 3u) << 4)) - 32;
+            ls[r][1] = (int) ((sl >> 4) | (((sh >> 2) & 3u) << 4)) - 32;
+#pragma unroll
+            for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { lo[r][sb][k] = iq4nl_lut4(cq[r][sb][k] & 0x0f0f0f0fu); hi[r][sb][k] = iq4nl_lut4((cq[r][sb][k] >> 4) & 0x0f0f0f0fu); }
+        }
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) {
+            const char * im = mmv_lds + c * img + (size_t) ibc * 256 + 64 * qq;
+            u32x4 a[2][2];
+#pragma unroll
+            for (int sb = 0; sb < 2; ++sb) { a[sb][0] = *(const u32x4 *) (im + 32 * sb); a[sb][1] = *(const u32x4 *) (im + 32 * sb + 16); }
+            const float yd = *(const float *) (mmv_lds + c * img + K + K / 8 + ibc * 4);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const bool rv = valid && (cgrp * ROWS + r) < nrows;
+                int isum = 0;
+#pragma unroll
+                for (int sb = 0; sb < 2; ++sb) {
+                    int s = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s = dot4(lo[r][sb][k], a[sb][0][k], dot4(hi[r][sb][k], a[sb][1][k], s));
+                    isum += ls[r][sb] * s;
+                }
+                const float t = (float) isum * (dx[r] * yd);
+                acc[r][c] += rv ? t : 0.0f;
             }
         }
         if (cit == nit - 1) {
@@ -506,6 +726,32 @@ static void mmv_q40_t(const mmv_args & a0, hipStream_t st) {
 }
 void mmv_q4_0(const mmv_args & a, hipStream_t st) { mmv_q40_t<false>(a, st); }
 void mmv_q5_0(const mmv_args & a, hipStream_t st) { mmv_q40_t<true>(a, st); }
+
+static long g_iq4_launches[2] = { 0, 0 };
+long mmv_iq4_launches(bool xs) { return g_iq4_launches[xs ? 1 : 0]; }
+template <bool XS>
+static void mmv_iq4_t(const mmv_args & a0, hipStream_t st) {
+    if (a0.nrows == 0 || a0.ncols == 0) return;
+    const size_t ib = XS ? q8k_image_bytes(a0.K) : q80_image_bytes(a0.K);
+    split_cols(a0, ib, [&](const mmv_args & a) {
+        mmv_kernel_t k = nullptr; int rows = 2;
+        switch (a.ncols) {
+            case 1: k = XS ? k_mmv_iq4xs<1, 2> : k_mmv_iq4nl<1, 2>; break;
+            case 2: k = XS ? k_mmv_iq4xs<2, 2> : k_mmv_iq4nl<2, 2>; break;
+            case 3: k = XS ? k_mmv_iq4xs<3, 2> : k_mmv_iq4nl<3, 2>; break;
+            case 4: k = XS ? k_mmv_iq4xs<4, 2> : k_mmv_iq4nl<4, 2>; break;
+            case 5: k = XS ? k_mmv_iq4xs<5, 1> : k_mmv_iq4nl<5, 1>; rows = 1; break;
+            case 6: k = XS ? k_mmv_iq4xs<6, 1> : k_mmv_iq4nl<6, 1>; rows = 1; break;
+            case 7: k = XS ? k_mmv_iq4xs<7, 1> : k_mmv_iq4nl<7, 1>; rows = 1; break;
+            case 8: k = XS ? k_mmv_iq4xs<8, 1> : k_mmv_iq4nl<8, 1>; rows = 1; break;
+            default: abort();
+        }
+        launch_mmv(k, rows, ib * a.ncols, a, st);
+        ++g_iq4_launches[XS ? 1 : 0];
+    });
+}
+void mmv_iq4_nl(const mmv_args & a, hipStream_t st) { mmv_iq4_t<false>(a, st); }
+void mmv_iq4_xs(const mmv_args & a, hipStream_t st) { mmv_iq4_t<true>(a, st); }
 
 #define MMVF_LAUNCH(NC, ROWS, WF16)                                                                                    \
     do {                                                                                                               \

@@ -19,6 +19,7 @@ __all__ = [
 GGML_TYPE_F32, GGML_TYPE_F16, GGML_TYPE_Q8_0 = 0, 1, 8
 GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_K = 12, 14, 15
 GGML_TYPE_I32, GGML_TYPE_I64 = 26, 27
+GGML_TYPE_IQ4_NL, GGML_TYPE_IQ4_XS = 20, 23
 GGML_ROPE_TYPE_NORMAL, GGML_ROPE_TYPE_NEOX = 0, 2
 GGML_PREC_F32 = 10
 GGML_BACKEND_BUFFER_USAGE_ANY, GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_BACKEND_BUFFER_USAGE_COMPUTE = 0, 1, 2   # ggml-backend.h:49-53
@@ -49,6 +50,7 @@ _TRAITS = {  # type -> (block elements, block bytes, numpy dtype or None)
     GGML_TYPE_I32: (1, 4, np.int32), GGML_TYPE_I64: (1, 8, np.int64),
     2: (32, 18, None), 3: (32, 20, None), 6: (32, 22, None), 7: (32, 24, None),      # Q4_0 Q4_1 Q5_0 Q5_1
     10: (256, 84, None), 11: (256, 110, None), 13: (256, 176, None),                # Q2_K Q3_K Q5_K
+    GGML_TYPE_IQ4_NL: (32, 18, None), GGML_TYPE_IQ4_XS: (256, 136, None),
     30: (1, 2, np.uint16),                                                          # BF16 (as raw 16-bit words)
 }
 

@@ -10,8 +10,8 @@ import math
 
 import numpy as np
 
-from .ggml import (GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_ROPE_TYPE_NEOX, GGML_TYPE_F16, GGML_TYPE_F32, GGML_TYPE_I32, GGML_TYPE_I64, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K,
-                   GGML_TYPE_Q8_0, Context, row_size)
+from .ggml import (GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_ROPE_TYPE_NEOX, GGML_TYPE_F16, GGML_TYPE_F32, GGML_TYPE_I32, GGML_TYPE_I64, GGML_TYPE_IQ4_NL,
+                   GGML_TYPE_IQ4_XS, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_0, Context, row_size)
 
 QWEN3_8B = dict(n_embd=4096, n_layer=36, n_head=32, n_head_kv=8, head_dim=128, n_ff=12288, n_vocab=151936,
                 rms_eps=1e-6, rope_base=1e6, n_ctx_orig=40960)
@@ -34,6 +34,24 @@ def q4_k_m_types(cfg):
         hi = GGML_TYPE_Q6_K if use_more_bits(i, n) else GGML_TYPE_Q4_K
         t[i] = dict(attn_q=GGML_TYPE_Q4_K, attn_k=GGML_TYPE_Q4_K, attn_v=hi, attn_output=GGML_TYPE_Q4_K,
                     ffn_gate=GGML_TYPE_Q4_K, ffn_up=GGML_TYPE_Q4_K, ffn_down=hi)
+    return t
+
+
+def iq4_xs_types(cfg, base=GGML_TYPE_IQ4_XS):
+    """Tensor-type map of an IQ4_XS file quantised without an imatrix (llama-quant.cpp; base=GGML_TYPE_IQ4_NL: the same rules for
+    LLAMA_FTYPE_MOSTLY_IQ4_NL): output Q6_K (:212-233, the default branch), attn_v Q5_K when n_gqa >= 4 (:299), ffn_down Q5_K in the first
+    n_layer/8 layers (:366), everything else the base type (:570-571) -- demoted to IQ4_NL where the row width is not a multiple of 256 (:463)."""
+    n = cfg["n_layer"]
+    gqa = cfg["n_head"] // cfg["n_head_kv"]
+
+    def fit(ty, K):
+        return GGML_TYPE_IQ4_NL if ty == GGML_TYPE_IQ4_XS and K % 256 != 0 else ty
+
+    E, HD, F = cfg["n_embd"], cfg["n_head"] * cfg["head_dim"], cfg["n_ff"]
+    t = {"output": GGML_TYPE_Q6_K}
+    for i in range(n):
+        t[i] = dict(attn_q=fit(base, E), attn_k=fit(base, E), attn_v=13 if gqa >= 4 else fit(base, E), attn_output=fit(base, HD),
+                    ffn_gate=fit(base, E), ffn_up=fit(base, E), ffn_down=13 if i < n // 8 else fit(base, F))          # 13: GGML_TYPE_Q5_K
     return t
 
 
@@ -100,6 +118,20 @@ def random_blocks(rng, ty, nrows, K, std=0.02):
         blk[..., 2:4] = _f16_bits(d * 15.5)[..., None].view(np.uint8).reshape(nrows, nb, 2)
         blk[..., 4:] = rng.integers(0, 256, size=(nrows, nb, 172), dtype=np.uint8)
         return blk.reshape(nrows, nb * 176)
+    if ty == GGML_TYPE_IQ4_NL:                               # value = d * kvalues_iq4nl[q]: rms of the table ~ 67
+        nb = K // 32
+        blk = np.empty((nrows, nb, 18), dtype=np.uint8)
+        d = (std / 67.0) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., 0:2] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        blk[..., 2:] = rng.integers(0, 256, size=(nrows, nb, 16), dtype=np.uint8)
+        return blk.reshape(nrows, nb * 18)
+    if ty == GGML_TYPE_IQ4_XS:                               # value = d * (ls - 32) * kvalues_iq4nl[q], ls in [0, 63]: rms ~ 18.5 * 67
+        nb = K // 256
+        blk = np.empty((nrows, nb, 136), dtype=np.uint8)
+        d = (std / 1240.0) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., 0:2] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        blk[..., 2:] = rng.integers(0, 256, size=(nrows, nb, 134), dtype=np.uint8)     # scales_h, scales_l[4], qs[128]
+        return blk.reshape(nrows, nb * 136)
     raise ValueError(ty)
 
 

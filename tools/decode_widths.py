@@ -1,6 +1,6 @@
 """tg128 (llama-bench test_gen analogue, bench.py's Decoder) at the widths of the target's siblings, with the batch-1 kernels (mmv1.hip; the
 TAIL instances when K % 4096 != 0) and with them switched off (the round-1 multi-column family).  Random Q4_K_M-mapped weights of each shape.
-  python tools/decode_widths.py"""
+  python tools/decode_widths.py [--models qwen3-8b] [--types q4_k_m,iq4_xs] [--mv1 1]"""
 import os
 import sys
 import time
@@ -18,12 +18,19 @@ MODELS = {
 
 
 def main():
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default=",".join(MODELS))
+    ap.add_argument("--types", default="q4_k_m", help="comma list: q4_k_m (qwen3.q4_k_m_types), iq4_xs (qwen3.iq4_xs_types, the mixed map of an IQ4_XS file)")
+    ap.add_argument("--mv1", default="1,0")
+    args = ap.parse_args()
     pkg = bench.load_pkg()
     from llama_cpp_omni_amd import qwen3
     be = pkg.Backend()
-    for name, cfg in MODELS.items():
-        types = qwen3.q4_k_m_types(cfg)
-        for mv1 in (1, 0):
+    for name, cfg in ((m, MODELS[m]) for m in args.models.split(",")):
+      for tname in args.types.split(","):
+        types = qwen3.q4_k_m_types(cfg) if tname == "q4_k_m" else qwen3.iq4_xs_types(cfg)
+        for mv1 in (int(v) for v in args.mv1.split(",")):
             be.set_option("mv1", mv1)
             d = bench.Decoder(pkg, be, cfg, types, n_ctx=512, n_kv=256)
             for t in range(16):
@@ -32,7 +39,7 @@ def main():
             for t in range(16, 144):
                 d.step(t)
             dt = time.perf_counter() - t0
-            print(f"{name:18s} mv1={mv1}  tg128 {128 / dt:7.1f} tok/s  ({dt / 128 * 1e3:.3f} ms/token, {be.get_stat('kernels_last_graph'):.0f} launches)", flush=True)
+            print(f"{name:18s} {tname:7s} mv1={mv1}  tg128 {128 / dt:7.1f} tok/s  ({dt / 128 * 1e3:.3f} ms/token, {be.get_stat('kernels_last_graph'):.0f} launches)", flush=True)
             d.g.free(); d.model.wctx.free()
     be.set_option("mv1", 1)
 

@@ -4,7 +4,7 @@ C-ABI.  One cgraph holds N MUL_MAT nodes over N *distinct* weight tensors (N x b
 Infinity Cache cannot serve re-reads) that share one activation vector; the graph is replayed a few times and timed
 with HIP events on the backend's stream.  Reports us per mat-vec and algorithmic GB/s (weight bytes / time).
 
-usage: python tools/mmv_bench.py [--types q4_K,q6_K] [--shapes 4096x4096,...] [--reps 5] [--ncols 1]
+usage: python tools/mmv_bench.py [--types q4_K,q6_K] [--shapes 4096x4096,...] [--reps 5] [--ncols 1] [--mv1 0]
 """
 import argparse
 import os
@@ -15,7 +15,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import load_pkg  # noqa: E402
 
-TYPES = {"q4_K": 12, "q6_K": 14, "q8_0": 8, "f16": 1, "q4_0": 2, "q5_K": 13}
+TYPES = {"q4_K": 12, "q6_K": 14, "q8_0": 8, "f16": 1, "q4_0": 2, "q5_K": 13, "iq4_nl": 20, "iq4_xs": 23}
 
 
 def main():
@@ -26,11 +26,14 @@ def main():
     ap.add_argument("--ncols", type=int, default=1)
     ap.add_argument("--min-mib", type=int, default=768)
     ap.add_argument("--pair", action="store_true")
+    ap.add_argument("--mv1", type=int, default=-1, help="option mv1 (0: Q4_K / Q6_K single columns on the register-load kernels of mmvk.hip instead of the batch-1 forms)")
     args = ap.parse_args()
     pkg = load_pkg()
     from llama_cpp_omni_amd import qwen3
     from llama_cpp_omni_amd.ggml import GGML_TYPE_F32, Context, row_size
     be = pkg.backend(0)
+    if args.mv1 >= 0:
+        be.set_option("mv1", args.mv1)
     rng = np.random.default_rng(0)
     for tname in args.types.split(","):
         ty = TYPES[tname]
@@ -50,6 +53,7 @@ def main():
                     ys.append(c.swiglu_split(gate, up))
             else:
                 ys = [c.mul_mat(w, x) for w in ws]
+            assert be.supports_op(ys[0]), f"{tname} {M}x{K}: MUL_MAT not admitted by this library"     # (graph_compute does not ask)
             c.alloc()
             host = qwen3.random_blocks(rng, ty, min(M, 4096), K)
             reps_rows = (M + host.shape[0] - 1) // host.shape[0]
