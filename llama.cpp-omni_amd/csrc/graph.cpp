@@ -400,6 +400,7 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmq_tile_launches"))  return (double) mi::mmq_tile_launches();
     if (!strcmp(key, "gemm_kq_launches"))   return (double) mi::gemm_variant_launches(3);
     if (!strcmp(key, "fattn_dma_launches")) return (double) mi::fattn_dma_launches();
+    if (!strcmp(key, "attn_vrows_launches")) return (double) mi::attn_vrows_launches();
     if (!strcmp(key, "fattn_gs_launches"))  return (double) mi::fattn_gs_launches();
     if (!strcmp(key, "fattn_gs_far_launches")) return (double) mi::fattn_gs_far_launches();
     if (!strcmp(key, "mmv_iq4nl_launches")) return (double) mi::mmv_iq4_launches(false);

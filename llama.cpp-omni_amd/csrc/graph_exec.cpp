@@ -417,11 +417,23 @@ bool can_hoist(exec_state & s, int i, int j, const int * item, int n_item) {
     }
     return true;
 }
-void note_write(exec_state & s, const ggml_tensor * t) {          // a kernel wrote t: drop the activation cache if it aliased
-    if (s.fa_mask) { const char * p = (const char *) t->data; if ((const char *) s.fa_mask >= p && (const char *) s.fa_mask < p + nbytes(t)) s.fa_mask = nullptr; }
-    if (!s.a_src) return;
+void note_write(exec_state & s, const ggml_tensor * t) {          // a kernel wrote t: drop every cache computed from bytes it overlaps (any part of them, not just the first)
     const byte_range r = range_of(t);
+    if (s.fa_mask && overlap(r, { s.fa_mask_lo, s.fa_mask_hi })) s.fa_mask = nullptr;
+    if (s.rt.pos && (overlap(r, { s.rt.lo, s.rt.hi }) || (s.rt.ff_lo && overlap(r, { s.rt.ff_lo, s.rt.ff_hi })))) s.rt.pos = nullptr;
+    if (!s.a_src) return;
     if (r.lo < s.a_range_hi && s.a_range_lo < r.hi) s.a_src = nullptr;
+}
+// the rope table in rope_scratch now holds the angles of (pos, ff, T, D, rp): T positions and D / 2 frequency factors were read
+void rt_remember(exec_state & s, const void * pos, const void * ff, int T, int D, const rope_params & rp) {
+    s.rt.pos = pos; s.rt.ff = ff; s.rt.T = T; s.rt.D = D; s.rt.rp = rp;
+    s.rt.lo = (const char *) pos; s.rt.hi = (const char *) pos + (size_t) T * 4;
+    s.rt.ff_lo = (const char *) ff; s.rt.ff_hi = ff ? (const char *) ff + (size_t) (D / 2) * 4 : nullptr;
+}
+void fa_mask_remember(exec_state & s, const ggml_tensor * mk, int64_t nq) {      // the tile map in fa_scratch is now the one of mask `mk` against nq query rows
+    const byte_range r = range_of(mk);
+    s.fa_mask = mk->data; s.fa_dims[0] = mk->ne[0]; s.fa_dims[1] = nq; s.fa_dims[2] = mk->ne[2]; s.fa_dims[3] = mk->ne[3]; s.fa_mnb1 = mk->nb[1];
+    s.fa_mask_lo = r.lo; s.fa_mask_hi = r.hi;
 }
 
 // ---- deferred norm (see exec_state::pn)
@@ -495,7 +507,7 @@ void compute_node(exec_state & s, int i) {
                 if (!valid) {
                     prof_scope ps(s, "rope", 0);
                     rope_table(P.pos, P.ff, P.rp, 1, a.D, (float *) s.c->rope_scratch, s.st); ++s.n_kernels;
-                    s.rt.pos = P.pos; s.rt.ff = P.ff; s.rt.T = 1; s.rt.D = a.D; s.rt.rp = P.rp;
+                    rt_remember(s, P.pos, P.ff, 1, a.D, P.rp);
                 }
                 a.rope_tab = (const float *) s.c->rope_scratch;
                 {
@@ -792,7 +804,7 @@ void compute_node(exec_state & s, int i) {
                 if (!valid) {
                     prof_scope ps(s, "rope", 0);
                     rope_table(P.pos, P.ff, P.rp, 1, D, (float *) s.c->rope_scratch, s.st); ++s.n_kernels;
-                    s.rt.pos = P.pos; s.rt.ff = P.ff; s.rt.T = 1; s.rt.D = D; s.rt.rp = P.rp;
+                    rt_remember(s, P.pos, P.ff, 1, D, P.rp);
                 }
                 f.rope_tab = (const float *) s.c->rope_scratch;
                 one = true;
@@ -847,8 +859,7 @@ void compute_node(exec_state & s, int i) {
                 f.map_valid = s.fa_mask == mk->data && s.fa_dims[0] == mk->ne[0] && s.fa_dims[1] == n->src[0]->ne[1] && s.fa_dims[2] == mk->ne[2] &&
                               s.fa_dims[3] == mk->ne[3] && s.fa_mnb1 == mk->nb[1];
                 if (!f.map_valid) {
-                    s.fa_mask = mk->data; s.fa_dims[0] = mk->ne[0]; s.fa_dims[1] = n->src[0]->ne[1]; s.fa_dims[2] = mk->ne[2]; s.fa_dims[3] = mk->ne[3];
-                    s.fa_mnb1 = mk->nb[1]; ++s.n_kernels;
+                    fa_mask_remember(s, mk, n->src[0]->ne[1]); ++s.n_kernels;
                 }
             }
             {
@@ -948,7 +959,7 @@ void copy_flush(exec_state & s) {
         s.n_copies_batched += n; s.c->stat_copies_batched += n;
     }
     ++s.n_kernels;
-    s.cq.clear(); s.cq_dead.clear(); s.vplain.t = nullptr;
+    s.cq.clear(); s.cq_dead.clear();
 }
 static bool same_desc(const tdesc & a, const tdesc & b) {
     if (a.p != b.p) return false;
@@ -1022,6 +1033,7 @@ void run_nodes(exec_state & s, ggml_cgraph * g) {
     s.g = g;
     s.done.assign(g->n_nodes, 0);
     s.index.clear(); s.users.clear(); s.lazy.clear(); s.lazy_base_deadline.clear(); s.gs = {};
+    s.vplain.t = nullptr;                                    // (only the attention launch that reads the rows clears it within a graph: a copy flush in between must not)
     s.cq.clear();
     if (s.c->opt_fusion) {
         s.index.reserve(g->n_nodes * 2); s.users.reserve(g->n_nodes * 2);

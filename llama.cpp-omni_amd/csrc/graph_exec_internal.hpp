@@ -67,6 +67,8 @@ int next_real_node(exec_state & s, int i);
 bool ready_before(exec_state & s, const ggml_tensor * src, int i, const int * item, int n_item);
 bool can_hoist(exec_state & s, int i, int j, const int * item, int n_item);
 void note_write(exec_state & s, const ggml_tensor * t);
+void rt_remember(exec_state & s, const void * pos, const void * ff, int T, int D, const rope_params & rp);
+void fa_mask_remember(exec_state & s, const ggml_tensor * mk, int64_t nq);
 void materialise_reduce(exec_state & s);
 void materialise_group(exec_state & s, int skip_mask = 0);
 bool reads_pending_group(exec_state & s, const ggml_tensor * n);

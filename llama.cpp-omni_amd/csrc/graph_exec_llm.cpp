@@ -184,6 +184,7 @@ bool exec_gemm_group(exec_state & s, int i) {
             const ggml_tensor * R = g->nodes[ri];
             if (is_out(s, R) || R->ne[2] != 1 || R->ne[3] != 1 || R->nb[0] != 4 || R->nb[1] != (size_t) R->ne[0] * 4) continue;
             const ggml_tensor * t = R; int cj = -1;
+            bool vrows = false; tdesc vrows_v;                             // (the V-rows layout: committed to s.vplain only once this launch has taken the CAST below)
             for (int hop = 0; hop < 5; ++hop) {
                 const int u = sole_user(s, t);
                 if (u < 0) break;
@@ -220,9 +221,9 @@ bool exec_gemm_group(exec_state & s, int i) {
                     auto i1 = M1n ? s.index.find(M1n) : s.index.end();
                     if (i1 != s.index.end() && i1->second > cj && M1n->op == GGML_OP_MUL_MAT && M * 2 % 16 == 0 && ((uintptr_t) Cp->data & 15) == 0 && exec_attn_sm_prefill(s, i1->second, true)) {
                         ms = 2; rs = (size_t) M * 2;
-                        s.vplain.t = Cp;
-                        s.vplain.v.p = Cp->data; s.vplain.v.ne[0] = Dh; s.vplain.v.ne[1] = N; s.vplain.v.ne[2] = S->ne[2]; s.vplain.v.ne[3] = 1;
-                        s.vplain.v.nb[0] = 2; s.vplain.v.nb[1] = (size_t) M * 2; s.vplain.v.nb[2] = (size_t) Dh * 2; s.vplain.v.nb[3] = (size_t) M * 2 * (size_t) N;
+                        vrows = true;
+                        vrows_v.p = Cp->data; vrows_v.ne[0] = Dh; vrows_v.ne[1] = N; vrows_v.ne[2] = S->ne[2]; vrows_v.ne[3] = 1;
+                        vrows_v.nb[0] = 2; vrows_v.nb[1] = (size_t) M * 2; vrows_v.nb[2] = (size_t) Dh * 2; vrows_v.nb[3] = (size_t) M * 2 * (size_t) N;
                     }
                 }
             }
@@ -235,6 +236,7 @@ bool exec_gemm_group(exec_state & s, int i) {
             a.m[q].y16 = (uint16_t *) Cp->data; a.m[q].y16_ms = ms; a.m[q].y16_rs = rs; a.m[q].y32 = false;
             if (add_idx[q] < 0) { a.m[q].dst = (float *) R->data; a.m[q].dst_cs = R->nb[1]; }
             cpy_idx[q] = cj;
+            if (vrows) { s.vplain.t = Cp; s.vplain.v = vrows_v; }
         }
     double flops = 0;
     for (int q = 0; q < a.nmat; ++q) flops += 2.0 * (double) a.m[q].M * (double) N * (double) K;
@@ -1037,7 +1039,7 @@ bool exec_rms_norm(exec_state & s, int i) {
                     a.rope_tab = (float *) s.c->rope_scratch;
                     a.rope_tab_valid = s.rt.pos == A.pos->data && s.rt.ff == (A.ff ? A.ff->data : nullptr) && s.rt.T == A.T && s.rt.D == A.D &&
                                        memcmp(&s.rt.rp, &A.rp, sizeof(rope_params)) == 0;
-                    if (!a.rope_tab_valid) { s.rt.pos = A.pos->data; s.rt.ff = A.ff ? A.ff->data : nullptr; s.rt.T = A.T; s.rt.D = A.D; s.rt.rp = A.rp; ++s.n_kernels; }
+                    if (!a.rope_tab_valid) { rt_remember(s, A.pos->data, A.ff ? A.ff->data : nullptr, A.T, A.D, A.rp); ++s.n_kernels; }
                 }
                 if (s.prm.n) {
                     // every job of this launch reads one of the pending results whole, each result once: point the jobs at the slabs; anything else gets the reduction launch
@@ -1167,6 +1169,8 @@ bool exec_rms_norm(exec_state & s, int i) {
 // PERMUTE -> CONT is one flash-attention launch reading V^T as it lies (reference: ggml_compute_forward_soft_max_f32, ops.cpp:5072-5182, between two ggml_compute_forward_mul_mat;
 // the [n_kv, n_q, H] blocks -- 146 MB written and read back per Whisper layer -- are never materialised).  An f32 mask is cast to f16 once per graph run (what the
 // reference's own flash-attention graphs do, llama-graph.cpp build_attn_inp_kv: ggml_cast(kq_mask, F16); 0 and -inf are exact) behind the mask tile map in the attention scratch.
+static long g_attn_vrows_launches = 0;
+long attn_vrows_launches() { return g_attn_vrows_launches; }
 bool exec_attn_sm_prefill(exec_state & s, int i, bool dry) {       // dry: would this MUL_MAT be taken?  (no launches, no state)
     static const bool off = getenv("MI355X_NO_ATTN_SM_PREFILL") != nullptr;
     ggml_cgraph * g = s.g;
@@ -1216,7 +1220,8 @@ bool exec_attn_sm_prefill(exec_state & s, int i, bool dry) {       // dry: would
     f.mask = nullptr; f.sinks = nullptr; f.scale = op_param_f32(SM, 0); f.max_bias = 0.0f; f.logit_softcap = 0.0f;
     f.scratch = nullptr; f.scratch_bytes = 0;
     if (!fattn_sm_prefill_ok(f)) { if (vplain) { fprintf(stderr, "[mi355x] exec_attn_sm_prefill: the chain whose V was written as rows is refused\n"); abort(); } return false; }
-    if (vplain && !dry) { f.v = s.vplain.v; f.v_transposed = false; s.vplain.t = nullptr; }
+    // (every check above and below depends only on the graph and the scratch sizes, which the dry run at exec_gemm_group saw the same: a chain accepted there is accepted here)
+    if (vplain && !dry) { f.v = s.vplain.v; f.v_transposed = false; s.vplain.t = nullptr; ++g_attn_vrows_launches; }
     if (mk) {
         const size_t map_b0 = attn_sm_mask16_off(nq, nkv), m16_b0 = mk->type == GGML_TYPE_F32 ? (size_t) mk->ne[1] * (size_t) nkv * 2 : 0;
         if (!s.c->fa_scratch || s.c->fa_scratch_bytes < map_b0 + m16_b0) return false;
@@ -1234,7 +1239,7 @@ bool exec_attn_sm_prefill(exec_state & s, int i, bool dry) {       // dry: would
             m = m16;
         }
         f.mask = &m; f.scratch = s.c->fa_scratch; f.scratch_bytes = map_b; f.map_valid = valid;
-        if (!valid) { s.fa_mask = mk->data; s.fa_dims[0] = mk->ne[0]; s.fa_dims[1] = nq; s.fa_dims[2] = mk->ne[2]; s.fa_dims[3] = mk->ne[3]; s.fa_mnb1 = mk->nb[1]; ++s.n_kernels; }
+        if (!valid) { fa_mask_remember(s, mk, nq); ++s.n_kernels; }
     }
     // the CONT's rows [D * H, nq * ns] read only by GEMMs (wo): emit them in f16 from the kernel
     const ggml_tensor * xg16 = nullptr;

@@ -719,7 +719,7 @@ bool exec_concat_tail(exec_state & s, int i) {
         src.p = (char *) x->data + (size_t) (f0 - P) * x->nb[1]; src.ne[1] = keep;
         const copy_pair cp = { src, td(n3), 4 };
         if (copy_queue_on(s) && copy_batch_ok(cp.src, cp.dst, 4)) copy_queue(s, &cp, 1, cp.dst, n3);
-        else { cpy_strided(src, GGML_TYPE_F32, td(n3), GGML_TYPE_F32, s.st); ++s.n_kernels; }
+        else { copy_flush(s); cpy_strided(src, GGML_TYPE_F32, td(n3), GGML_TYPE_F32, s.st); ++s.n_kernels; }      // (x may be the output of a copy still queued)
     }
     note_write(s, n3);
     for (int k : { n0 ? j1 : -1, j2, j3 }) if (k >= 0) { s.done[k] = 1; ++s.n_fused; }

@@ -79,15 +79,17 @@ struct exec_state {
     // one-token attention left as slices' partial states in fa_scratch (fattn_one.hip k_fattn_gs): `n` = the FLASH_ATTN_EXT node whose f32 rows were NOT written, `consumer` = the
     // one MUL_MAT (wo) that folds them in its prologue (mv1_source); anything else that runs first materialises the rows (gs_materialise in graph_exec.cpp)
     struct { const ggml_tensor * n = nullptr; int consumer = -1; int nh = 0, D = 0; } gs;
-    // (pos, rope parameters) whose (cos, sin) table currently sits in rope_scratch (prefill: shared by every layer of the graph)
-    struct { const void * pos = nullptr; const void * ff = nullptr; int T = 0, D = 0; rope_params rp; } rt;
-    // mask whose tile map currently sits in fa_scratch
-    const void *  fa_mask = nullptr; int64_t fa_dims[4] = {0, 0, 0, 0}; size_t fa_mnb1 = 0;
+    // (pos, rope parameters) whose (cos, sin) table currently sits in rope_scratch (prefill: shared by every layer of the graph); [lo, hi) / [ff_lo, ff_hi): the bytes of
+    // the positions and frequency factors the table was computed from -- a node that writes any of them drops the table (note_write)
+    struct { const void * pos = nullptr; const void * ff = nullptr; int T = 0, D = 0; rope_params rp; const char * lo = nullptr, * hi = nullptr, * ff_lo = nullptr, * ff_hi = nullptr; } rt;
+    // mask whose tile map currently sits in fa_scratch; [fa_mask_lo, fa_mask_hi): the mask's bytes (a write into any row of it drops the map, note_write)
+    const void *  fa_mask = nullptr; int64_t fa_dims[4] = {0, 0, 0, 0}; size_t fa_mnb1 = 0; const char * fa_mask_lo = nullptr, * fa_mask_hi = nullptr;
     // a V^T that a fused soft-max attention will read where it LIES (a transposed V cache) instead of from the CONT + CAST copies the graph makes of it: `cast` = the CAST node the
     // attention's second mat-mul names, `v` = the same elements in the cache (try_alias_vt in graph_exec.cpp)
     struct { const ggml_tensor * cast = nullptr; tdesc v; int cont_i = -1, cast_i = -1; } va;
     // an encoder's V^T CAST tensor `t` whose bytes were written as V ROWS instead ([D, n_tokens, H] like K: the GEMM epilogue that makes the f16 copy chooses the layout): its one
     // reader, the flash-attention-off chain exec_attn_sm_prefill fuses, then runs as plain flash attention on the LDS-DMA ring kernel (head size 64); set by exec_gemm_group
+    // once the launch that writes the rows has taken the CAST, cleared by the attention launch that reads them (and at the start of run_nodes) -- nothing else
     struct { const ggml_tensor * t = nullptr; tdesc v; } vplain;
     // deferred split-K reduction of a GROUPED launch (wq / wk / wv of a prefill ubatch): the results A[0..n) still lie as `nsplit` slabs in gemm_partial (slab = `slab` floats,
     // matrix q a dense [N][M[q]] block at + off[q]); the q / k norm + rope + store launch behind them sums the slabs itself (k_norm_rope_v4), anybody else gets materialise_group
@@ -163,5 +165,6 @@ size_t graph_gemm_partial_need(const ggml_cgraph * g);
 bool ensure_scratch(backend_ctx * c, void ** p, size_t * have, size_t need);
 // ---- graph_exec.cpp
 bool mm_takes_gemm_any(const ggml_tensor * n);
+long attn_vrows_launches();                           // flash-attention-off chains run on V rows that exec_gemm_group wrote (graph_exec_llm.cpp)
 void run_nodes(exec_state & s, ggml_cgraph * g);
 } // namespace mi
