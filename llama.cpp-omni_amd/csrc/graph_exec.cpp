@@ -2,7 +2,6 @@
 // rules, compute_node and run_nodes.  The fusion matchers live beside it since round 6: graph_exec_llm.cpp (text decoder), graph_exec_t2w.cpp (encoders / Token2Wav);
 // shared declarations in graph_exec_internal.hpp.  (Split out of graph.cpp in round 4, by module in round 6; no behaviour change.)
 #include "graph_exec_internal.hpp"
-#include <map>
 
 namespace mi {
 
@@ -13,9 +12,8 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
     if (s.pn.m && x == s.pn.m) materialise_norm(s);                      // a consumer outside the in-kernel-norm launches
     if (kind == ACT_F32) return 0;
     if (kind == ACT_Q8KT && (ne12 != 1 || ne13 != 1 || x->type != GGML_TYPE_F32)) { fprintf(stderr, "[mi355x] prepare_act: the block-major Q8_K image takes one 2-D f32 activation\n"); abort(); }
-    const bool cached = s.a_src == x->data && s.a_kind == kind && s.a_K == K && s.a_ne[0] == N && s.a_ne[1] == ne12 &&
-                        s.a_ne[2] == ne13 && s.a_nb[0] == x->nb[1] && s.a_nb[1] == x->nb[2] && s.a_nb[2] == x->nb[3];
-    if (cached) return img;
+    if (s.act.holds(x, kind)) return img;
+    void * const act = act_begin(s);
     auto conv = [&](const float * src, size_t xs, void * out, int64_t rows) {
         if      (kind == ACT_Q8K) quantize_q8k_image(src, xs, out, K, rows, s.st);
         else if (kind == ACT_Q8KT) quantize_q8k_tile_image(src, xs, out, K, rows, s.st);
@@ -29,24 +27,22 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
     if (x->type == GGML_TYPE_F16) {
         // F16 x F16 (the MUL_MAT of ggml_conv_1d / ggml_conv_2d: im2col columns against an f16 kernel): the activation rows are already
         // in the GEMM's format; gather them into the dense image (supports_op admits F16 src1 only next to F16 src0)
-        tdesc d; d.p = s.c->act_scratch; d.ne[0] = K; d.ne[1] = N; d.ne[2] = ne12; d.ne[3] = ne13;
+        tdesc d; d.p = act; d.ne[0] = K; d.ne[1] = N; d.ne[2] = ne12; d.ne[3] = ne13;
         d.nb[0] = 2; d.nb[1] = img; d.nb[2] = img * (size_t) N; d.nb[3] = img * (size_t) (N * ne12);
         cpy_strided(td(x), GGML_TYPE_F16, d, GGML_TYPE_F16, s.st);
         ++s.n_kernels;
     } else if (flat) {
-        conv((const float *) x->data, x->nb[1], s.c->act_scratch, N * ne12 * ne13);
+        conv((const float *) x->data, x->nb[1], act, N * ne12 * ne13);
     } else if (kind == ACT_F16 && N * ne12 * ne13 <= 65535) {      // (ACT_F16Q never gets here: K-quant weights take 2-D activations in every graph the planner sends to the GEMM)            // permuted rows (q seen per head): one strided launch
-        convert_f32_f16_rows3((const float *) x->data, x->nb[1], x->nb[2], x->nb[3], N, ne12, ne13, (uint16_t *) s.c->act_scratch, img, K, s.st);
+        convert_f32_f16_rows3((const float *) x->data, x->nb[1], x->nb[2], x->nb[3], N, ne12, ne13, (uint16_t *) act, img, K, s.st);
         ++s.n_kernels;
     } else {
         for (int64_t i13 = 0; i13 < ne13; ++i13)
             for (int64_t i12 = 0; i12 < ne12; ++i12)
                 conv((const float *) ((const char *) x->data + i12 * x->nb[2] + i13 * x->nb[3]), x->nb[1],
-                     (char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N) * img, N);
+                     (char *) act + (size_t) ((i13 * ne12 + i12) * N) * img, N);
     }
-    s.a_src = x->data; s.a_kind = kind; s.a_K = K; s.a_ne[0] = N; s.a_ne[1] = ne12; s.a_ne[2] = ne13;
-    s.a_nb[0] = x->nb[1]; s.a_nb[1] = x->nb[2]; s.a_nb[2] = x->nb[3];
-    s.a_range_lo = (const char *) x->data; s.a_range_hi = (const char *) x->data + nbytes(x);
+    s.act.seed(x, kind);
     return img;
 }
 
@@ -94,7 +90,7 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out
         prepare_act(s, x, ACT_Q8KT);
         mmqt_args q;
         q.nmat = 1; q.m[0] = { w->data, w->nb[1], (float *) dst->data, dst->nb[1], M }; q.img = s.c->act_scratch; q.N = N; q.K = K;
-        if (dst->nb[1] % 16 == 0 && gemm_split_scratch_bytes(M, N, K) <= s.c->gemm_partial_bytes) { q.partial = (float *) s.c->gemm_partial; q.partial_bytes = s.c->gemm_partial_bytes; }
+        if (dst->nb[1] % 16 == 0 && gemm_split_scratch_bytes(M, N, K) <= s.c->gemm_partial_bytes) { q.partial = (float *) gemm_partial_take(s); q.partial_bytes = s.c->gemm_partial_bytes; }
         prof_scope ps(s, "mmq_tile", 2.0 * (double) M * (double) N * (double) K);
         mmq_tile(q, s.st);
         ++s.n_kernels;
@@ -161,8 +157,7 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out
         int64_t k_done = 0;
         // the producer (SOFT_MAX of an encoder's / a flash-attention-off prefill's scores, or an earlier mat-mul on the same x) left the f16 image of x in
         // the scratch -- and possibly did not write the f32 block at all
-        bool x_img = w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && s.a_src == x->data && s.a_kind == ACT_F16 && s.a_K == K && s.a_ne[0] == N && s.a_ne[1] == ne12 &&
-                     s.a_ne[2] == ne13 && s.a_nb[0] == x->nb[1] && s.a_nb[1] == x->nb[2] && s.a_nb[2] == x->nb[3];
+        bool x_img = w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && s.act.holds(x, ACT_F16);
         // F16 weights, K a few columns past a multiple of 64 (SigLip2's n_ff 4304): the F16 MFMA GEMM takes the first K - K % 64 columns, this kernel adds the tail
         if (w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && ne12 * ne13 == 1 && K % 64 != 0 && K >= 512 && w->nb[1] % 16 == 0 && ((uintptr_t) w->data & 15) == 0 &&
             out->nb[1] % 16 == 0 && act_image_bytes(ACT_F16, K) * (size_t) N <= s.c->act_scratch_bytes) {
@@ -173,7 +168,7 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out
             gemm_multi_args ga;                                  // (split along K when the tiles do not fill the chip: SigLip2's fc2, 1152 x 1024 outputs, went from 79 to 24 us)
             ga.nmat = 1; ga.m[0] = { (const uint16_t *) w->data, w->nb[1], (float *) out->data, out->nb[1], M, nullptr, 0 };
             ga.X = (const uint16_t *) s.c->act_scratch; ga.x_rs = ximg; ga.N = N; ga.K = k_done;
-            ga.partial = gemm_split_scratch_bytes(M, N, k_done) <= s.c->gemm_partial_bytes ? (float *) s.c->gemm_partial : nullptr; ga.partial_bytes = s.c->gemm_partial_bytes;
+            ga.partial = gemm_split_scratch_bytes(M, N, k_done) <= s.c->gemm_partial_bytes ? (float *) gemm_partial_take(s) : nullptr; ga.partial_bytes = s.c->gemm_partial_bytes;
             gemm_f16_multi(ga, s.st);
             ++s.n_kernels;
         }
@@ -186,11 +181,7 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out
         }
         a.dst = (float *) out->data; a.dst_cs = out->nb[1]; a.dst_nb2 = out->nb[2]; a.dst_nb3 = out->nb[3]; a.accumulate = k_done > 0; a.bias = bias; a.act = act;
         a.M = M; a.N = N; a.K = K - k_done; a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
-        if (s.c->gemm_partial && !s.c->fa_counters && !s.capturing) {      // (first use is an eager submission: captures come from the second on)
-            if (hipMalloc((void **) &s.c->fa_counters, 1024 * sizeof(unsigned)) == hipSuccess) HIP_CHECK(hipMemsetAsync(s.c->fa_counters, 0, 1024 * sizeof(unsigned), s.st));
-            else { (void) hipGetLastError(); s.c->fa_counters = nullptr; }
-        }
-        if (s.c->gemm_partial && s.c->fa_counters) { a.partial = (float *) s.c->gemm_partial; a.partial_bytes = s.c->gemm_partial_bytes; a.counters = s.c->fa_counters; a.n_counters = 1024; }
+        if (s.c->gemm_partial && fa_counters(s)) { a.partial = (float *) gemm_partial_take(s); a.partial_bytes = s.c->gemm_partial_bytes; a.counters = s.c->fa_counters; a.n_counters = 1024; }
         if (nsib > 0 && sib_taken) {
             *sib_taken = false;
             if (k_done == 0 && !x_img && w->type == GGML_TYPE_F32 && x->type == GGML_TYPE_F32) {
@@ -327,12 +318,12 @@ bool mv1_node_ok(exec_state & s, const ggml_tensor * n) {
 void gs_materialise(exec_state & s) {
     if (!s.gs.n) return;
     prof_scope ps(s, "fattn", 0);
-    fattn_gs_merge((const float *) s.c->fa_scratch, (float *) s.gs.n->data, s.gs.nh, s.gs.D, s.st); ++s.n_kernels;
+    fattn_gs_merge((const float *) fa_scratch_take(s, FA_GS_SLICES), (float *) s.gs.n->data, s.gs.nh, s.gs.D, s.st); ++s.n_kernels;
     s.gs.n = nullptr; s.gs.consumer = -1;
 }
 void mv1_source(exec_state & s, const ggml_tensor * x, const ggml_tensor * const * outs, int n_outs, int n_consumers, mv1_args & v) {
     if (s.gs.n && x->data == s.gs.n->data) {
-        mv1_args t = v; t.x = nullptr; t.norm_w = nullptr; t.img = nullptr; t.parts = (const float *) s.c->fa_scratch; t.nslice = fattn_gs_nslice();
+        mv1_args t = v; t.x = nullptr; t.norm_w = nullptr; t.img = nullptr; t.parts = (const float *) fa_scratch_take(s, FA_GS_SLICES); t.nslice = fattn_gs_nslice();
         if (!(s.pn.m && x == s.pn.m) && x->ne[0] == (int64_t) s.gs.nh * s.gs.D && mmv2_enabled() && mmv2_ok(t)) {
             v.parts = t.parts; v.nslice = t.nslice; v.x = nullptr; v.norm_w = nullptr; v.img = nullptr;
             s.gs.n = nullptr; s.gs.consumer = -1; ++s.n_fused;
@@ -345,10 +336,8 @@ void mv1_source(exec_state & s, const ggml_tensor * x, const ggml_tensor * const
         v.x = nr.x; v.norm_w = nr.w; v.eps = nr.eps;
         return;
     }
-    const int64_t K = x->ne[0];
     const act_kind kind = v.m[0].type == GGML_TYPE_Q8_0 ? ACT_Q80 : (v.m[0].type == GGML_TYPE_F16 ? ACT_F16 : ACT_Q8K);       // (v.m[] is filled before the source is chosen)
-    const bool cached = s.a_src == x->data && s.a_kind == kind && s.a_K == K && s.a_ne[0] == 1 && s.a_ne[1] == x->ne[2] && s.a_ne[2] == x->ne[3];
-    bool plain = !cached && !(s.pn.m && x == s.pn.m) && ((uintptr_t) x->data & 15) == 0;
+    bool plain = !s.act.holds_row(x, kind) && !(s.pn.m && x == s.pn.m) && ((uintptr_t) x->data & 15) == 0;
     if (plain) {
         const byte_range rx = range_of(x);
         for (int i = 0; i < n_outs; ++i) if (outs[i] && overlap(range_of(outs[i]), rx)) plain = false;
@@ -418,22 +407,32 @@ bool can_hoist(exec_state & s, int i, int j, const int * item, int n_item) {
     return true;
 }
 void note_write(exec_state & s, const ggml_tensor * t) {          // a kernel wrote t: drop every cache computed from bytes it overlaps (any part of them, not just the first)
-    const byte_range r = range_of(t);
-    if (s.fa_mask && overlap(r, { s.fa_mask_lo, s.fa_mask_hi })) s.fa_mask = nullptr;
-    if (s.rt.pos && (overlap(r, { s.rt.lo, s.rt.hi }) || (s.rt.ff_lo && overlap(r, { s.rt.ff_lo, s.rt.ff_hi })))) s.rt.pos = nullptr;
-    if (!s.a_src) return;
-    if (r.lo < s.a_range_hi && s.a_range_lo < r.hi) s.a_src = nullptr;
+    const byte_range w = range_of(t);
+    s.mask_map.invalidate(w); s.rt.invalidate(w); s.act.invalidate(w);
 }
-// the rope table in rope_scratch now holds the angles of (pos, ff, T, D, rp): T positions and D / 2 frequency factors were read
-void rt_remember(exec_state & s, const void * pos, const void * ff, int T, int D, const rope_params & rp) {
-    s.rt.pos = pos; s.rt.ff = ff; s.rt.T = T; s.rt.D = D; s.rt.rp = rp;
-    s.rt.lo = (const char *) pos; s.rt.hi = (const char *) pos + (size_t) T * 4;
-    s.rt.ff_lo = (const char *) ff; s.rt.ff_hi = ff ? (const char *) ff + (size_t) (D / 2) * 4 : nullptr;
+const float * ensure_rope_table(exec_state & s, const int32_t * pos, const float * ff, const rope_params & rp, int T, int D) {
+    if (!s.rt.holds(pos, ff, T, D, rp)) {
+        prof_scope ps(s, "rope", 0);
+        rope_table(pos, ff, rp, T, D, (float *) s.c->rope_scratch, s.st); ++s.n_kernels;
+        s.rt.remember(pos, ff, T, D, rp);
+    }
+    return (const float *) s.c->rope_scratch;
 }
-void fa_mask_remember(exec_state & s, const ggml_tensor * mk, int64_t nq) {      // the tile map in fa_scratch is now the one of mask `mk` against nq query rows
-    const byte_range r = range_of(mk);
-    s.fa_mask = mk->data; s.fa_dims[0] = mk->ne[0]; s.fa_dims[1] = nq; s.fa_dims[2] = mk->ne[2]; s.fa_dims[3] = mk->ne[3]; s.fa_mnb1 = mk->nb[1];
-    s.fa_mask_lo = r.lo; s.fa_mask_hi = r.hi;
+void * fa_scratch_take(exec_state & s, fa_tenant who, const ggml_tensor * node) {
+    if (s.gs.n && who != FA_GS_SLICES && node != s.gs.n) { fprintf(stderr, "[mi355x] graph_compute: the attention scratch is taken (tenant %d) while the slices of %s are pending in it\n", (int) who, s.gs.n->name); abort(); }
+    if (who != FA_MASK_MAP) s.mask_map.drop();
+    return s.c->fa_scratch;
+}
+unsigned * fa_counters(exec_state & s) {
+    if (!s.c->fa_counters && !s.capturing) {                         // (first use is always an eager submission: captures come from the second on)
+        if (hipMalloc((void **) &s.c->fa_counters, 1024 * sizeof(unsigned)) == hipSuccess) HIP_CHECK(hipMemsetAsync(s.c->fa_counters, 0, 1024 * sizeof(unsigned), s.st));
+        else { (void) hipGetLastError(); s.c->fa_counters = nullptr; }
+    }
+    return s.c->fa_counters;
+}
+void * gemm_partial_take(exec_state & s) {
+    if (s.pr.A || s.prm.n) { fprintf(stderr, "[mi355x] graph_compute: a split-K launch takes the slab scratch while a deferred reduction is pending in it\n"); abort(); }
+    return s.c->gemm_partial;
 }
 
 // ---- deferred norm (see exec_state::pn)
@@ -442,12 +441,10 @@ void materialise_norm(exec_state & s) {                           // run the sta
     s.pn.m = nullptr;
     {
         prof_scope ps(s, "rms_norm_mul_quant", 0);
-        rms_norm_mul_quant((const float *) x->data, x->nb[1], (const float *) wt->data, (float *) m->data, m->nb[1], s.c->act_scratch, m->ne[0], m->ne[1], s.pn.eps, s.st);
+        rms_norm_mul_quant((const float *) x->data, x->nb[1], (const float *) wt->data, (float *) m->data, m->nb[1], act_begin(s), m->ne[0], m->ne[1], s.pn.eps, s.st);
     }
     ++s.n_kernels;
-    s.a_src = m->data; s.a_kind = ACT_Q8K; s.a_K = m->ne[0]; s.a_ne[0] = m->ne[1]; s.a_ne[1] = 1; s.a_ne[2] = 1;
-    s.a_nb[0] = m->nb[1]; s.a_nb[1] = m->nb[2]; s.a_nb[2] = m->nb[3];
-    s.a_range_lo = (const char *) m->data; s.a_range_hi = (const char *) m->data + nbytes(m);
+    s.act.seed(m, ACT_Q8K);                                       // (2-D: exec_rms_norm defers only [K, N, 1, 1] norms)
 }
 // may the launch that writes `outs` take its activation from the pending norm of x?  (it reads the norm's INPUT while it runs)
 bool norm_in_kernel(exec_state & s, const ggml_tensor * x, const ggml_tensor * const * outs, int n_outs, int n_consumers, mmv_norm & nr) {
@@ -486,13 +483,19 @@ bool reads_pending_group(exec_state & s, const ggml_tensor * n) {          // an
     return false;
 }
 
+void settle(exec_state & s, std::initializer_list<const ggml_tensor *> reads) {
+    if (s.pr.A) materialise_reduce(s);
+    if (s.prm.n) materialise_group(s);
+    if (s.pn.m) for (const ggml_tensor * t : reads) if (t == s.pn.m) { materialise_norm(s); break; }
+}
+
 // ------------------------------------------------------------------------------------------------ node dispatch
 void compute_node(exec_state & s, int i) {
     ggml_cgraph * g = s.g;
     ggml_tensor * n = g->nodes[i];
     if (is_noop(n)) return;
-    if (s.pr.A && !((n->op == GGML_OP_RMS_NORM || n->op == GGML_OP_NORM) && n->src[0] == s.pr.A)) materialise_reduce(s);      // somebody else reads the split-K result first
-    if (s.prm.n && !reads_pending_group(s, n)) materialise_group(s);
+    // somebody else than the norm that takes the slabs reads a split-K result first (a norm whose matcher turns them down settles itself)
+    if (!(s.pr.A && (n->op == GGML_OP_RMS_NORM || n->op == GGML_OP_NORM) && n->src[0] == s.pr.A) && !(s.prm.n && reads_pending_group(s, n))) settle(s);
 
     switch (n->op) {
         case GGML_OP_MUL_MAT:
@@ -500,25 +503,7 @@ void compute_node(exec_state & s, int i) {
                 if (n->src[0]->type == GGML_TYPE_F32 && n->src[1]->type == GGML_TYPE_F32 && exec_attn_f32(s, i)) return;
                 lazy_net(s, i);
             }
-            if (s.pq.sm && s.pq.fa == i) {                                // flash-attention off, one token: K.q, soft-max, V^T.p, permute + cont and the q / k / v pre-stage in one launch
-                const fattn_pre & P = s.pq.pre;
-                attn_sm_args & a = s.pq.sma;
-                const bool valid = s.rt.pos == (const void *) P.pos && s.rt.ff == (const void *) P.ff && s.rt.T == 1 && s.rt.D == a.D && memcmp(&s.rt.rp, &P.rp, sizeof(rope_params)) == 0;
-                if (!valid) {
-                    prof_scope ps(s, "rope", 0);
-                    rope_table(P.pos, P.ff, P.rp, 1, a.D, (float *) s.c->rope_scratch, s.st); ++s.n_kernels;
-                    rt_remember(s, P.pos, P.ff, 1, a.D, P.rp);
-                }
-                a.rope_tab = (const float *) s.c->rope_scratch;
-                {
-                    prof_scope ps(s, "fattn", 0);
-                    attn_one_sm(a, s.st); ++s.n_kernels;
-                }
-                s.done[s.pq.sm_soft] = 1; s.done[s.pq.sm_mm2] = 1; s.done[s.pq.sm_cont] = 1; s.n_fused += 3;
-                note_write(s, g->nodes[s.pq.sm_cont]); note_write(s, g->nodes[s.pq.kst]); note_write(s, g->nodes[s.pq.vst]);
-                s.pq.fa = -1; s.pq.sm = false;
-                return;
-            }
+            if (s.pq.sm && s.pq.fa == i) { exec_attn_sm_decode(s, i); return; }
             if (exec_attn_sm_prefill(s, i, false)) return;
             if (exec_attn_f32(s, i)) return;
             if (s.va.cast && (n->src[0] == s.va.cast || g->nodes[i]->src[1]->op == GGML_OP_SOFT_MAX)) materialise_vt(s);
@@ -537,15 +522,14 @@ void compute_node(exec_state & s, int i) {
         case GGML_OP_NORM: {
             if (exec_norm_modulate(s, i)) return;
             if (exec_norm(s, i)) return;
-            if (s.pr.A) materialise_reduce(s);
+            settle(s);
             prof_scope ps(s, "norm", 0);
             norm_f32(td(n->src[0]), td(n), op_param_f32(n, 0), s.st); ++s.n_kernels;
             break;
         }
         case GGML_OP_RMS_NORM: {
             if (exec_rms_norm(s, i)) return;
-            if (s.pr.A) materialise_reduce(s);
-            if (s.prm.n) materialise_group(s);
+            settle(s);
             prof_scope ps(s, "rms_norm", 0);
             rms_norm(td(n->src[0]), td(n), op_param_f32(n, 0), nullptr, s.st); ++s.n_kernels;
             break;
@@ -645,7 +629,7 @@ void compute_node(exec_state & s, int i) {
             const bool w32 = !(emit16 && u1 > i && next_real_node(s, i) == u1);
             {
                 prof_scope ps(s, "unary", 0);
-                unary_f32(op_param_i32(n, 0), (const float *) n->src[0]->data, (float *) n->data, nelements(n), s.st, emit16 ? (uint16_t *) s.c->act_scratch : nullptr, w32);
+                unary_f32(op_param_i32(n, 0), (const float *) n->src[0]->data, (float *) n->data, nelements(n), s.st, emit16 ? (uint16_t *) act_begin(s) : nullptr, w32);
             }
             ++s.n_kernels;
             if (emit16) { note_write(s, n); seed_act_f16(s, xg); ++s.n_fused; return; }
@@ -671,19 +655,17 @@ void compute_node(exec_state & s, int i) {
             if (xq) {
                 {
                     prof_scope ps(s, "glu", 0);
-                    swiglu_q8k(td(n->src[0]), b, td(n), true, s.c->act_scratch, s.st);      // (f32 too: the image cache may be dropped before the consumer runs)
+                    swiglu_q8k(td(n->src[0]), b, td(n), true, act_begin(s), s.st);      // (f32 too: the image cache may be dropped before the consumer runs)
                 }
                 ++s.n_kernels; ++s.n_fused;
                 note_write(s, n);
-                s.a_src = xq->data; s.a_kind = ACT_Q8K; s.a_K = xq->ne[0]; s.a_ne[0] = xq->ne[1]; s.a_ne[1] = 1; s.a_ne[2] = 1;
-                s.a_nb[0] = xq->nb[1]; s.a_nb[1] = xq->nb[2]; s.a_nb[2] = xq->nb[3];
-                s.a_range_lo = (const char *) xq->data; s.a_range_hi = (const char *) xq->data + nbytes(xq);
+                s.act.seed(xq, ACT_Q8K);                            // (2-D: kq_mm_ok)
                 return;
             }
             {
                 prof_scope ps(s, "glu", 0);
                 if (emit16) glu_f32(op_param_i32(n, 0), td(n->src[0]), n->src[1] ? &b : nullptr, op_param_i32(n, 1) != 0, td(n), s.st,
-                                    (uint16_t *) s.c->act_scratch, act_image_bytes(ACT_F16, n->ne[0]), n_users(s, n) > 1);
+                                    (uint16_t *) act_begin(s), act_image_bytes(ACT_F16, n->ne[0]), n_users(s, n) > 1);
                 else        glu_f32(op_param_i32(n, 0), td(n->src[0]), n->src[1] ? &b : nullptr, op_param_i32(n, 1) != 0, td(n), s.st);
             }
             ++s.n_kernels;
@@ -693,10 +675,7 @@ void compute_node(exec_state & s, int i) {
         }
         case GGML_OP_ROPE: {
             if (s.c->opt_fusion && exec_rope_chain(s, i)) return;
-            rope_params rp;
-            rp.n_dims = op_param_i32(n, 1); rp.mode = op_param_i32(n, 2); rp.n_ctx_orig = op_param_i32(n, 4);
-            rp.freq_base = op_param_f32(n, 5); rp.freq_scale = op_param_f32(n, 6); rp.ext_factor = op_param_f32(n, 7);
-            rp.attn_factor = op_param_f32(n, 8); rp.beta_fast = op_param_f32(n, 9); rp.beta_slow = op_param_f32(n, 10);
+            const rope_params rp = rope_params_of(n);
             prof_scope ps(s, "rope", 0);
             rope_f32(td(n->src[0]), (const int32_t *) n->src[1]->data, n->src[2] ? (const float *) n->src[2]->data : nullptr, td(n), rp, s.st); ++s.n_kernels;
             break;
@@ -718,12 +697,10 @@ void compute_node(exec_state & s, int i) {
             prof_scope ps(s, "soft_max", 0);
             soft_max_f32(td(n->src[0]), n->src[1] ? &m : nullptr, n->src[1] ? n->src[1]->type : 0,
                          n->src[2] ? (const float *) n->src[2]->data : nullptr, td(n), op_param_f32(n, 0), op_param_f32(n, 1), s.st,
-                         xg ? (uint16_t *) s.c->act_scratch : nullptr, xg ? act_image_bytes(ACT_F16, n->ne[0]) : 0, xg == nullptr);
+                         xg ? (uint16_t *) act_begin(s) : nullptr, xg ? act_image_bytes(ACT_F16, n->ne[0]) : 0, xg == nullptr);
             ++s.n_kernels;
             if (xg) {
-                s.a_src = xg->data; s.a_kind = ACT_F16; s.a_K = xg->ne[0]; s.a_ne[0] = xg->ne[1]; s.a_ne[1] = xg->ne[2]; s.a_ne[2] = xg->ne[3];
-                s.a_nb[0] = xg->nb[1]; s.a_nb[1] = xg->nb[2]; s.a_nb[2] = xg->nb[3];
-                s.a_range_lo = (const char *) xg->data; s.a_range_hi = (const char *) xg->data + nbytes(xg);
+                s.act.seed(xg, ACT_F16);
                 ++s.n_fused;
                 return;                                             // (no note_write: the f32 block was not written)
             }
@@ -748,7 +725,7 @@ void compute_node(exec_state & s, int i) {
                 if (n->op == GGML_OP_CONT && src->type == GGML_TYPE_F32 && n->type == GGML_TYPE_F32 && n->ne[2] == 1 && n->ne[3] == 1 && n->nb[1] == (size_t) n->ne[0] * 4 &&
                     cu > i && next_real_node(s, i) == cu && n_users(s, n) == 1 && gemm_only_consumers(s, n, n->ne[0], n->ne[1], &xg)) {
                     copy_flush(s);
-                    tdesc d; d.p = s.c->act_scratch; d.ne[0] = n->ne[0]; d.ne[1] = n->ne[1]; d.ne[2] = 1; d.ne[3] = 1;
+                    tdesc d; d.p = act_begin(s); d.ne[0] = n->ne[0]; d.ne[1] = n->ne[1]; d.ne[2] = 1; d.ne[3] = 1;
                     const size_t img = act_image_bytes(ACT_F16, n->ne[0]);
                     d.nb[0] = 2; d.nb[1] = img; d.nb[2] = img * (size_t) n->ne[1]; d.nb[3] = d.nb[2];
                     cpy_strided(td(src), GGML_TYPE_F32, d, GGML_TYPE_F16, s.st);
@@ -784,99 +761,7 @@ void compute_node(exec_state & s, int i) {
             set_rows(td(n->src[0]), td(n->src[1]), n->src[1]->type, td(n), n->type, s.st, period); ++s.n_kernels;
             break;
         }
-        case GGML_OP_FLASH_ATTN_EXT: {
-            fattn_args f; tdesc m;
-            fill_fattn_args(n, f, m);
-            if ((n->src[0]->ne[0] != 64 && n->src[0]->ne[0] != 128) || n->src[2]->ne[0] != n->src[0]->ne[0] || n->src[1]->type != GGML_TYPE_F16) {      // other head sizes / cache types: the generic kernel, no fused stage
-                prof_scope ps(s, "fattn", 0);
-                flash_attn_ext_f16(f, s.st); ++s.n_kernels;
-                break;
-            }
-            const bool with_pre = s.pq.fa == i;
-            if (with_pre) f.pre = &s.pq.pre;
-            // one token over a shallow cache: the latency-optimised kernel (fattn_one.hip) takes the token's (cos, sin) from a table that is
-            // computed once per graph, and leaves the Q8_K image to wo's own prologue
-            bool one = false;
-            if (with_pre && fattn_one_ok(f) && s.c->rope_scratch_bytes >= (size_t) n->src[0]->ne[0] * 4) {
-                const fattn_pre & P = s.pq.pre;
-                const int D = (int) n->src[0]->ne[0];
-                const bool valid = s.rt.pos == (const void *) P.pos && s.rt.ff == (const void *) P.ff && s.rt.T == 1 && s.rt.D == D && memcmp(&s.rt.rp, &P.rp, sizeof(rope_params)) == 0;
-                if (!valid) {
-                    prof_scope ps(s, "rope", 0);
-                    rope_table(P.pos, P.ff, P.rp, 1, D, (float *) s.c->rope_scratch, s.st); ++s.n_kernels;
-                    rt_remember(s, P.pos, P.ff, 1, D, P.rp);
-                }
-                f.rope_tab = (const float *) s.c->rope_scratch;
-                one = true;
-                // ... as one workgroup per (KV head, 64-row slice) when the ONE reader of the rows is the next launching node, a batch-1 K-quant mat-vec the LDS-DMA engine
-                // takes (wo): the slices' partial states stay in fa_scratch and that launch folds them in its prologue (mv1_source) -- the f32 rows are never written
-                const int u = s.c->opt_fusion && !is_out(s, n) ? sole_user(s, n) : -1;        // (option "fattn_gs" / MI355X_FA_NO_GS: inside fattn_gs_ok)
-                if (u > i && next_real_node(s, i) == u && fattn_gs_ok(f) && s.c->fa_scratch && s.c->fa_scratch_bytes >= fattn_gs_parts_bytes((int) n->ne[1], D) && mmv2_enabled()) {
-                    const ggml_tensor * c = g->nodes[u];
-                    const ggml_tensor * x = c->op == GGML_OP_MUL_MAT ? c->src[1] : nullptr;
-                    if (x && x->data == n->data && x->ne[0] == n->ne[0] * n->ne[1] && x->ne[1] == 1 && x->ne[2] == 1 && x->ne[3] == 1 && x != s.pn.m && mv1_node_ok(s, c)) {                 // (K-quant or Q8_0 wo: mmv2_ok decides)
-                        mv1_args t; t.nmat = 1; t.K = x->ne[0];
-                        t.m[0] = { c->src[0]->data, c->src[0]->nb[1], (float *) c->data, 0, nullptr, 0, c->src[0]->ne[1], (int) c->src[0]->type };
-                        t.parts = (const float *) s.c->fa_scratch; t.nslice = fattn_gs_nslice();
-                        if (mmv2_ok(t)) { f.gs_parts = (float *) s.c->fa_scratch; s.gs.n = n; s.gs.consumer = u; s.gs.nh = (int) n->ne[1]; s.gs.D = D; s.fa_mask = nullptr; }
-                    }
-                }
-            }
-            // epilogue fusion: when the attention output only feeds K-quant mat-vecs (wo), emit its Q8_K image here
-            const ggml_tensor * xuse = nullptr;
-            if (!one && s.c->opt_fusion && n->ne[3] == 1 && n->ne[2] <= 32 && n_users(s, n) > 0 && !is_out(s, n) &&
-                rms_norm_mul_quant_ok(n->ne[0] * n->ne[1]) && fattn_can_emit_image(f)) {
-                bool ok = true;
-                for (int u : s.users[n]) {
-                    const ggml_tensor * c = g->nodes[u];
-                    const ggml_tensor * x = c->op == GGML_OP_MUL_MAT ? c->src[1] : nullptr;
-                    if (!x || !kq_mm_ok(c) || x->data != n->data || x->ne[0] != n->ne[0] * n->ne[1] || x->ne[1] != n->ne[2] ||
-                        x->nb[1] != (size_t) x->ne[0] * 4 || (xuse && !same_act(xuse, x))) { ok = false; break; }
-                    xuse = x;
-                }
-                if (!ok) xuse = nullptr;
-            }
-            if (xuse) f.img = s.c->act_scratch;
-            // prefill: the attention output [D, H, nq, ns] read as [H*D, nq*ns] rows by wo's GEMM -> emit those rows in f16 from the kernel
-            const ggml_tensor * xg16 = nullptr;
-            if (!xuse && fattn_uses_mma(f) && n->nb[1] == (size_t) n->ne[0] * 4 && n->nb[2] == (size_t) n->ne[0] * n->ne[1] * 4 &&
-                n->nb[3] == n->nb[2] * (size_t) n->ne[2] && gemm_only_consumers(s, n, n->ne[0] * n->ne[1], n->ne[2] * n->ne[3], &xg16)) {
-                f.out16 = (uint16_t *) s.c->act_scratch; f.out16_rs = act_image_bytes(ACT_F16, n->ne[0] * n->ne[1]); f.write_f32 = n_users(s, n) > 1;
-            }
-            if (fattn_scratch_bytes(f) > 0 && !fattn_uses_mma(f)) {       // decode kernel at long context: workspace of its KV split
-                f.scratch = s.c->fa_scratch; f.scratch_bytes = s.c->fa_scratch_bytes;
-                if (!s.c->fa_counters && !s.capturing) {                  // (first use is always an eager submission: captures come from the second on)
-                    if (hipMalloc((void **) &s.c->fa_counters, 1024 * sizeof(unsigned)) == hipSuccess) HIP_CHECK(hipMemsetAsync(s.c->fa_counters, 0, 1024 * sizeof(unsigned), s.st));
-                    else { (void) hipGetLastError(); s.c->fa_counters = nullptr; }
-                }
-                f.counters = s.c->fa_counters;
-                s.fa_mask = nullptr;                                      // (the scratch no longer holds a mask tile map)
-                ++s.n_kernels;
-            } else if (fattn_scratch_bytes(f) > 0) {
-                // the mask tile map is computed once per mask tensor and graph run (every layer shares the mask)
-                const ggml_tensor * mk = n->src[3];
-                f.scratch = s.c->fa_scratch; f.scratch_bytes = s.c->fa_scratch_bytes;
-                f.map_valid = s.fa_mask == mk->data && s.fa_dims[0] == mk->ne[0] && s.fa_dims[1] == n->src[0]->ne[1] && s.fa_dims[2] == mk->ne[2] &&
-                              s.fa_dims[3] == mk->ne[3] && s.fa_mnb1 == mk->nb[1];
-                if (!f.map_valid) {
-                    fa_mask_remember(s, mk, n->src[0]->ne[1]); ++s.n_kernels;
-                }
-            }
-            {
-                prof_scope ps(s, "fattn", 0);
-                flash_attn_ext_f16(f, s.st); ++s.n_kernels;
-            }
-            note_write(s, n);
-            if (with_pre) { note_write(s, g->nodes[s.pq.kst]); note_write(s, g->nodes[s.pq.vst]); s.pq.fa = -1; }
-            if (xg16) { seed_act_f16(s, xg16); ++s.n_fused; }
-            if (xuse) {
-                s.a_src = xuse->data; s.a_kind = ACT_Q8K; s.a_K = xuse->ne[0]; s.a_ne[0] = xuse->ne[1]; s.a_ne[1] = 1; s.a_ne[2] = 1;
-                s.a_nb[0] = xuse->nb[1]; s.a_nb[1] = xuse->nb[2]; s.a_nb[2] = xuse->nb[3];
-                s.a_range_lo = (const char *) xuse->data; s.a_range_hi = (const char *) xuse->data + nbytes(xuse);
-                ++s.n_fused;
-            }
-            return;
-        }
+        case GGML_OP_FLASH_ATTN_EXT: exec_fattn(s, i); return;
         default:
             log_msg(GGML_LOG_LEVEL_ERROR, "[mi355x] graph_compute: op %d (%s) reached the backend but is not implemented -- supports_op bug\n", (int) n->op, n->name);
             abort();
@@ -1046,7 +931,7 @@ void run_nodes(exec_state & s, ggml_cgraph * g) {
                 while (t) {
                     auto & v = s.users[t];
                     if (v.empty() || v.back() != i) v.push_back(i);
-                    t = (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE) ? t->src[0] : nullptr;
+                    t = view_parent(t);
                 }
             }
         }
@@ -1104,7 +989,7 @@ void run_nodes(exec_state & s, ggml_cgraph * g) {
             const ggml_tensor * n_ = g->nodes[i];
             for (int k = 0; k < GGML_MAX_SRC; ++k) {
                 if (!n_->src[k] || !n_->src[k]->data) continue;
-                { bool lz = false; for (const ggml_tensor * t_ = n_->src[k]; t_; t_ = t_->view_src ? t_->view_src : ((t_->op == GGML_OP_RESHAPE || t_->op == GGML_OP_VIEW || t_->op == GGML_OP_PERMUTE || t_->op == GGML_OP_TRANSPOSE) ? t_->src[0] : nullptr)) if (s.lazy.count(t_)) lz = true; if (lz) continue; }
+                { bool lz = false; for (const ggml_tensor * t_ = n_->src[k]; t_; t_ = t_->view_src ? t_->view_src : view_parent(t_)) if (s.lazy.count(t_)) lz = true; if (lz) continue; }
                 const byte_range r = range_of(n_->src[k]);
                 for (const auto & d : s.cq_dead)
                     if (r.lo < d.hi && d.lo < r.hi)
@@ -1118,8 +1003,7 @@ void run_nodes(exec_state & s, ggml_cgraph * g) {
             for (size_t q = 0; q < s.cq_dead.size(); ) { if (w.lo < s.cq_dead[q].hi && s.cq_dead[q].lo < w.hi) s.cq_dead.erase(s.cq_dead.begin() + q); else ++q; }
         } } dead_g{ s, g->nodes[i] };
         {   // pending copies leave before anything that is not itself a plain copy (the copy-shaped matchers below flush where they launch)
-            const int op_ = g->nodes[i]->op;
-            if (!s.cq.empty() && !is_noop(g->nodes[i]) && op_ != GGML_OP_CONT && op_ != GGML_OP_CONCAT && op_ != GGML_OP_CPY && op_ != GGML_OP_DUP) copy_flush(s);
+            if (!s.cq.empty() && !is_noop(g->nodes[i]) && !is_plain_copy(g->nodes[i]->op)) copy_flush(s);
         }
         if (s.gs.n && i != s.gs.consumer && !is_noop(g->nodes[i]) && g->nodes[i] != s.gs.n) { copy_flush(s); gs_materialise(s); }       // (somebody else runs before wo folds the attention slices)
         if (g->nodes[i]->op == GGML_OP_IM2COL && exec_conv1d_tc(s, i)) continue;
@@ -1160,6 +1044,5 @@ void run_nodes(exec_state & s, ggml_cgraph * g) {
     gs_materialise(s);                                       // (the attention node was the graph's last launching node)
     if (launch_log && !s.capturing) { fprintf(launch_log, "== end of a graph of %d nodes\n", g->n_nodes); fflush(launch_log); }
 }
-
 
 } // namespace mi

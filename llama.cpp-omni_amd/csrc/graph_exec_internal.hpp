@@ -1,16 +1,15 @@
 // graph_exec_internal.hpp -- what the translation units of the executor share (round 6: graph_exec.cpp split by module): graph_exec.cpp = activation images,
 // the MUL_MAT executor, deferral bookkeeping, compute_node and run_nodes; graph_exec_llm.cpp = the text-decoder matchers (grouped GEMMs, norm / rope chains and their
 // hand-over to the attention launches, split-K folds); graph_exec_t2w.cpp = the encoder / Token2Wav matchers (f32 attention chain, element-wise chains, lazy copies,
-// streaming convolutions, modulated norms).  Pure movement: no function body changed.
+// streaming convolutions, modulated norms).
 #pragma once
 #include "graph_internal.hpp"
+#include <initializer_list>
 #include <map>
 
 namespace mi {
 
-
 // ------------------------------------------------------------------------------------------------ MUL_MAT
-struct byte_range { const char * lo; const char * hi; };
 // out / bias: the ADD of a [M] row vector behind the mat-mul, folded into the any-shape GEMM's epilogue (exec_mul_mat decides; only that path takes them)
 // sib / nsib: up to two more F32-weight mat-muls over the same activation (same weight shape and strides) for the launch; *sib_taken tells whether they went along
 struct mm_sibling { const ggml_tensor * w; const ggml_tensor * out; const float * bias; };
@@ -27,9 +26,6 @@ struct nr_chain {
 // the three element-wise nodes ride in the norm launch's epilogue, rounded as they round.  The norm has exactly these two readers.
 struct norm_mod_match { int mi_, a1i, a2i; const ggml_tensor * sv, * tv, * out; };
 
-static inline byte_range range_of(const ggml_tensor * t) { const char * p = (const char *) t->data; return { p, p + nbytes(t) }; }
-static inline bool overlap(byte_range a, byte_range b) { return a.lo < b.hi && b.lo < a.hi && a.lo != a.hi && b.lo != b.hi; }
-
 static inline bool is_kquant(int t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K; }   // the formats with integer-dot kernels on Q8_K activations
 // Is t read by somebody this executor does not see?  Graph outputs, and -- when the scheduler cut the graph into splits -- tensors whose
 // whole-graph use count (ggml_cgraph::use_counts, shared by the split views: ggml_graph_view) exceeds the uses inside this split: a later
@@ -38,6 +34,14 @@ static inline bool is_out(exec_state & s, const ggml_tensor * t) { return (t->fl
 
 static inline size_t attn_sm_mask16_off(int64_t nq, int64_t nkv) { return (fattn_map_bytes_host(nq, nkv) + 255) & ~(size_t) 255; }
 
+// the parameters of a ROPE node (zeroed first: rope_params are compared with memcmp)
+static inline rope_params rope_params_of(const ggml_tensor * r) {
+    rope_params rp; memset(&rp, 0, sizeof(rp));
+    rp.n_dims = op_param_i32(r, 1); rp.mode = op_param_i32(r, 2); rp.n_ctx_orig = op_param_i32(r, 4);
+    rp.freq_base = op_param_f32(r, 5); rp.freq_scale = op_param_f32(r, 6); rp.ext_factor = op_param_f32(r, 7);
+    rp.attn_factor = op_param_f32(r, 8); rp.beta_fast = op_param_f32(r, 9); rp.beta_slow = op_param_f32(r, 10);
+    return rp;
+}
 static inline tdesc swapped01(tdesc d) { std::swap(d.ne[0], d.ne[1]); std::swap(d.nb[0], d.nb[1]); return d; }
 
 // deferred copies (graph_exec.cpp): queue `nj` jobs of ONE node (they may write interleaved parts of one tensor: not checked against each other) / launch what is pending
@@ -51,7 +55,6 @@ byte_range range_of(const tdesc & d);
 size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind);
 const char * mmv_class(int type);
 const uint16_t * weight_shadow(exec_state & s, const ggml_tensor * w, const char * wp, int64_t K, int64_t M);
-bool mm_takes_gemm_any(const ggml_tensor * n);
 void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out = nullptr, const float * bias = nullptr, const mm_sibling * sib = nullptr, int nsib = 0, bool * sib_taken = nullptr, int act = 0);
 bool plain_kq_matvec(const ggml_tensor * n, int max_cols);
 bool kq_mm_ok(const ggml_tensor * n);
@@ -67,8 +70,19 @@ int next_real_node(exec_state & s, int i);
 bool ready_before(exec_state & s, const ggml_tensor * src, int i, const int * item, int n_item);
 bool can_hoist(exec_state & s, int i, int j, const int * item, int n_item);
 void note_write(exec_state & s, const ggml_tensor * t);
-void rt_remember(exec_state & s, const void * pos, const void * ff, int T, int D, const rope_params & rp);
-void fa_mask_remember(exec_state & s, const ggml_tensor * mk, int64_t nq);
+const float * ensure_rope_table(exec_state & s, const int32_t * pos, const float * ff, const rope_params & rp, int T, int D);      // the table of (pos, ff, rp) in rope_scratch: computed now unless s.rt holds it
+// One taker per shared scratch.  fa_scratch has four tenants: anybody but the mask map ends s.mask_map, and nobody but their producer (`node`, when the launching node may be
+// it) and consumers takes the buffer while attention slices are pending in it (s.gs: an abort).
+enum fa_tenant { FA_MASK_MAP, FA_GS_SLICES, FA_KV_SPLIT, FA_SM_PARTS };
+void * fa_scratch_take(exec_state & s, fa_tenant who, const ggml_tensor * node = nullptr);
+unsigned * fa_counters(exec_state & s);                          // the arrival counters of the split launches: allocated at first use outside capture (null: not available)
+void * gemm_partial_take(exec_state & s);                        // gemm_partial for a split-K launch that reduces at once: nothing deferred may lie in it (s.pr / s.prm: an abort)
+static inline void * act_begin(exec_state & s) { s.act.drop(); return s.c->act_scratch; }      // act_scratch for a launch that WRITES an image: ends the record, only seed() makes a new one
+// Make pending state real before a launch that reads memory outside the deferral-aware paths: s.pr and s.prm are reduced, s.pn is run when one of `reads` is its result.
+// compute_node settles in front of every node but the norm that takes the slabs; a matcher that run_nodes calls BEFORE compute_node settles itself -- or, like exec_ew_chain
+// and lazy_try_register, relies on this INVARIANT: exec_gemm_group defers a reduction only when the first launching node behind the result's own node is the (RMS_)NORM that
+// reads it (what an epilogue ADD was hoisted over cannot read it: can_hoist).  (At most one of s.pr / s.prm is pending: both are set at a MUL_MAT node, behind compute_node's settle.)
+void settle(exec_state & s, std::initializer_list<const ggml_tensor *> reads = {});
 void materialise_reduce(exec_state & s);
 void materialise_group(exec_state & s, int skip_mask = 0);
 bool reads_pending_group(exec_state & s, const ggml_tensor * n);
@@ -93,6 +107,8 @@ bool match_rope_only(exec_state & s, int j, nr_chain & c);
 bool exec_rope_chain(exec_state & s, int i);
 bool exec_rms_norm(exec_state & s, int i);
 bool exec_attn_f32(exec_state & s, int i);
+void exec_fattn(exec_state & s, int i);
+void exec_attn_sm_decode(exec_state & s, int i);
 void materialise_vt(exec_state & s);
 bool try_alias_vt(exec_state & s, int i);
 void compute_node(exec_state & s, int i);
@@ -102,6 +118,5 @@ bool lazy_try_register(exec_state & s, int i);
 bool exec_causal_conv(exec_state & s, int i);
 bool exec_concat_tail(exec_state & s, int i);
 bool exec_conv1d_tc(exec_state & s, int i);
-void run_nodes(exec_state & s, ggml_cgraph * g);
 
 } // namespace mi

@@ -115,12 +115,13 @@ bool exec_gemm_group(exec_state & s, int i) {
         }
         ++s.n_kernels; s.n_fused += 2;
         s.done[mm_idx[1]] = 1; s.done[glu_idx] = 1;
-        std::swap(s.c->act_scratch, s.c->act_scratch_alt); std::swap(s.c->act_scratch_bytes, s.c->act_scratch_alt_bytes);
+        std::swap(s.c->act_scratch, s.c->act_scratch_alt); std::swap(s.c->act_scratch_bytes, s.c->act_scratch_alt_bytes);      // (the image just written is the current one now)
+        s.act.drop();
         seed_act_f16(s, glu_x);
         return true;
     }
-    if (a.nmat == 1 && a.m[0].dst_cs % 16 == 0 && gemm_split_scratch_bytes(a.m[0].M, N, K) <= s.c->gemm_partial_bytes) a.partial = (float *) s.c->gemm_partial;
-    else if (a.nmat > 1 && N <= gemm_group_split_max_cols() && s.c->gemm_partial_bytes > 0) a.partial = (float *) s.c->gemm_partial;      // short prompts: split-K for the grouped launches too
+    if (a.nmat == 1 && a.m[0].dst_cs % 16 == 0 && gemm_split_scratch_bytes(a.m[0].M, N, K) <= s.c->gemm_partial_bytes) a.partial = (float *) gemm_partial_take(s);
+    else if (a.nmat > 1 && N <= gemm_group_split_max_cols() && s.c->gemm_partial_bytes > 0) a.partial = (float *) gemm_partial_take(s);      // short prompts: split-K for the grouped launches too
     a.partial_bytes = s.c->gemm_partial_bytes;
     // a streaming encoder chunk (<= 128 columns: split K, the result goes through the reduction launch): linear -> + bias -> + residual stream.  The second ADD
     // (only reader of the first, same shape, its other operand ready) rides in the reduction's epilogue too: (acc + bias) + residual, the two roundings of the two nodes.
@@ -138,7 +139,8 @@ bool exec_gemm_group(exec_state & s, int i) {
             if ((uop == GGML_UNARY_OP_GELU || uop == GGML_UNARY_OP_GELU_QUICK) && U->src[0] == A && U->type == GGML_TYPE_F32 && same_shape(U, A) && U->ne[2] == 1 && U->ne[3] == 1 && U->ne[0] % 8 == 0 &&
                 U->nb[0] == 4 && U->nb[1] == (size_t) U->ne[0] * 4 && ((uintptr_t) U->data & 15) == 0 && gemm_only_consumers(s, U, U->ne[0], U->ne[1], &xg)) {
                 const int u1 = sole_user(s, U);
-                a.m[0].unary = uop; a.m[0].y16 = (uint16_t *) s.c->act_scratch; a.m[0].y16_rs = act_image_bytes(ACT_F16, U->ne[0]);
+                a.m[0].unary = uop; a.m[0].y16 = (uint16_t *) act_begin(s);       // (the reduction launch writes it, behind the GEMM that read x's image)
+                a.m[0].y16_rs = act_image_bytes(ACT_F16, U->ne[0]);
                 a.m[0].y32 = !(u1 > u && next_real_node(s, u) == u1);
                 a.m[0].dst = (float *) U->data; a.m[0].dst_cs = U->nb[1];
                 un_idx = u; un_x = xg;
@@ -280,13 +282,14 @@ bool exec_gemm_group(exec_state & s, int i) {
         gemm_f16_multi(a, s.st);
     }
     ++s.n_kernels;
-    if (group_deferred && nsplit > 1) {
+    if (group_deferred && nsplit > 1) {                         // (settle's invariant: granted above only because the next launching node is the RMS_NORM that reads one of the results)
         s.prm.n = a.nmat; s.prm.nsplit = nsplit; s.prm.N = N;
         size_t off = 0;
         for (int q = 0; q < a.nmat; ++q) { s.prm.A[q] = g->nodes[mm_idx[q]]; s.prm.off[q] = off; s.prm.M[q] = a.m[q].M; off += (size_t) a.m[q].M * (size_t) N; }
         s.prm.slab = off;
         nsplit = 0;
     }
+    // (settle's invariant: granted above only because the first launching node behind Aout's own node is the (RMS_)NORM that reads it; what a hoisted ADD skipped cannot read it: can_hoist)
     if (nsplit > 1) { s.pr.A = Aout; s.pr.nsplit = nsplit; s.pr.resid = a.m[0].resid; s.pr.resid_cs = a.m[0].resid_cs; s.pr.resid2 = a.m[0].resid2; s.pr.resid2_cs = a.m[0].resid2_cs; }
     if (un_idx >= 0) {                                          // (the bias ADD's rows are never written: its one reader ran in the reduction)
         s.done[add_idx[0]] = 1; s.done[un_idx] = 1; s.n_fused += 2;
@@ -524,6 +527,16 @@ void exec_mul_mat(exec_state & s, int i) {
         else note_write(s, g->nodes[mm_idx[q]]);
     }
 }
+// the optional store of a ROPE node's rotated rows [D, H, T] into an f16 table (llama_kv_cache::cpy_k), the rope output's only consumer: its node index, or -1
+static int rope_store_of(exec_state & s, int ri) {
+    const ggml_tensor * r = s.g->nodes[ri];
+    const int si = sole_user(s, r);
+    if (si <= ri || s.g->nodes[si]->op != GGML_OP_SET_ROWS || s.done[si]) return -1;
+    const ggml_tensor * S = s.g->nodes[si], * V = S->src[0], * idx = S->src[1];
+    return V && idx && V->data == r->data && V->ne[0] == r->ne[0] * r->ne[1] && V->ne[1] == r->ne[2] && V->ne[2] == 1 && V->ne[3] == 1 &&
+           V->nb[1] == r->nb[2] && r->nb[1] == (size_t) r->ne[0] * 4 && S->type == GGML_TYPE_F16 && S->nb[0] == 2 &&
+           (idx->type == GGML_TYPE_I64 || idx->type == GGML_TYPE_I32) && idx->ne[0] == r->ne[2] && idx->ne[1] == 1 && idx->ne[2] == 1 ? si : -1;
+}
 bool match_norm_rope(exec_state & s, int j, nr_chain & c) {
     ggml_cgraph * g = s.g;
     ggml_tensor * n = g->nodes[j];
@@ -544,18 +557,8 @@ bool match_norm_rope(exec_state & s, int j, nr_chain & c) {
           pos->nb[0] == 4 && (!ff || (ff->type == GGML_TYPE_F32 && ff->nb[0] == 4)))) return false;
     c.norm = j; c.mul = mi_; c.rope = ri; c.store = -1; c.wt = wt; c.pos = pos; c.ff = ff; c.xin = n->src[0]; c.first = j;
     c.D = (int) D; c.H = (int) n->ne[1]; c.T = (int) n->ne[2]; c.eps = op_param_f32(n, 0);
-    memset(&c.rp, 0, sizeof(c.rp));
-    c.rp.n_dims = op_param_i32(r, 1); c.rp.mode = mode; c.rp.n_ctx_orig = op_param_i32(r, 4);
-    c.rp.freq_base = op_param_f32(r, 5); c.rp.freq_scale = op_param_f32(r, 6); c.rp.ext_factor = op_param_f32(r, 7);
-    c.rp.attn_factor = op_param_f32(r, 8); c.rp.beta_fast = op_param_f32(r, 9); c.rp.beta_slow = op_param_f32(r, 10);
-    // optional store of the rotated rows (llama_kv_cache::cpy_k): the rope output's only consumer
-    const int si = sole_user(s, r);
-    if (si > ri && g->nodes[si]->op == GGML_OP_SET_ROWS && !s.done[si]) {
-        const ggml_tensor * S = g->nodes[si], * V = S->src[0], * idx = S->src[1];
-        if (V && idx && V->data == r->data && V->ne[0] == D * n->ne[1] && V->ne[1] == n->ne[2] && V->ne[2] == 1 && V->ne[3] == 1 &&
-            V->nb[1] == r->nb[2] && r->nb[1] == (size_t) D * 4 && S->type == GGML_TYPE_F16 && S->nb[0] == 2 &&
-            (idx->type == GGML_TYPE_I64 || idx->type == GGML_TYPE_I32) && idx->ne[0] == n->ne[2] && idx->ne[1] == 1 && idx->ne[2] == 1) c.store = si;
-    }
+    c.rp = rope_params_of(r);
+    c.store = rope_store_of(s, ri);
     return true;
 }
 norm_rope_job chain_job(exec_state & s, const nr_chain & c) {
@@ -609,9 +612,7 @@ void seed_act_f16(exec_state & s, const ggml_tensor * x, bool quantised) {   // 
         requant_f16_rows_q8k((uint16_t *) s.c->act_scratch, act_image_bytes(ACT_F16, x->ne[0]), x->ne[0], x->ne[1] * x->ne[2] * x->ne[3], s.st);
         ++s.n_kernels;
     }
-    s.a_src = x->data; s.a_kind = want; s.a_K = x->ne[0]; s.a_ne[0] = x->ne[1]; s.a_ne[1] = 1; s.a_ne[2] = 1;
-    s.a_nb[0] = x->nb[1]; s.a_nb[1] = x->nb[2]; s.a_nb[2] = x->nb[3];
-    s.a_range_lo = (const char *) x->data; s.a_range_hi = (const char *) x->data + nbytes(x);
+    s.act.seed(x, want);                                                  // (2-D: gemm_only_consumers)
 }
 
 // The encoders' LayerNorm: NORM -> MUL by the [n] weight -> ADD of the [n] bias (audition.cpp / vision.cpp build_norm), each the next launching node
@@ -652,16 +653,17 @@ bool exec_norm(exec_state & s, int i) {
     // the rows still lie as split-K slabs of the mat-mul in front (+ bias / residual): summed, written and normalised in this launch
     const bool from_split = s.pr.A && s.pr.A == n->src[0];
     if (from_split && !norm_rows_from_split_ok(td(n->src[0]), td(out), s.pr.nsplit, s.pr.resid_cs, s.pr.resid2_cs, s.pr.resid, s.pr.resid2, s.c->gemm_partial)) materialise_reduce(s);
+    uint16_t * const img16 = emit16 ? (uint16_t *) act_begin(s) : nullptr;
     {
         prof_scope ps(s, "norm", 0);
         if (s.pr.A && s.pr.A == n->src[0]) {
             norm_rows_from_split(td(n->src[0]), td(out), op_param_f32(n, 0), (const float *) wt->data, bt ? (const float *) bt->data : nullptr,
-                                 emit16 ? (uint16_t *) s.c->act_scratch : nullptr, emit16 ? act_image_bytes(ACT_F16, out->ne[0]) : 0, w32,
+                                 img16, emit16 ? act_image_bytes(ACT_F16, out->ne[0]) : 0, w32,
                                  (const float *) s.c->gemm_partial, s.pr.nsplit, (size_t) n->src[0]->ne[0] * (size_t) n->src[0]->ne[1], s.pr.resid, s.pr.resid_cs, s.pr.resid2, s.pr.resid2_cs, s.st);
             s.pr.A = nullptr; ++s.n_fused;
         } else
         norm_rows_f32(td(n->src[0]), td(out), op_param_f32(n, 0), (const float *) wt->data, bt ? (const float *) bt->data : nullptr,
-                      emit16 ? (uint16_t *) s.c->act_scratch : nullptr, emit16 ? act_image_bytes(ACT_F16, out->ne[0]) : 0, w32, s.st);
+                      img16, emit16 ? act_image_bytes(ACT_F16, out->ne[0]) : 0, w32, s.st);
     }
     ++s.n_kernels;
     s.done[mi_] = 1; ++s.n_fused;
@@ -806,16 +808,107 @@ bool try_defer_qkv_to_softmax_attention(exec_state & s, const nr_chain & A, cons
     a.D = (int) D; a.nkv = (int) nkv; a.n_head = (int) H; a.n_head_kv = (int) HK; a.scale = op_param_f32(SM, 0);
     a.rope_tab = (const float *) s.c->rope_scratch;                                  // filled when the launch happens
     if (nkv > 256) {                                                                 // slices: partial rows in the attention scratch, arrival counters
-        if (!s.c->fa_counters && !s.capturing) {
-            if (hipMalloc((void **) &s.c->fa_counters, 1024 * sizeof(unsigned)) == hipSuccess) HIP_CHECK(hipMemsetAsync(s.c->fa_counters, 0, 1024 * sizeof(unsigned), s.st));
-            else { (void) hipGetLastError(); s.c->fa_counters = nullptr; }
-        }
-        a.part = s.c->fa_scratch; a.part_bytes = s.c->fa_scratch_bytes; a.counters = s.c->fa_counters;
-        s.fa_mask = nullptr;                                                         // (the scratch no longer holds a mask tile map)
+        a.part = fa_scratch_take(s, FA_SM_PARTS); a.part_bytes = s.c->fa_scratch_bytes; a.counters = fa_counters(s);      // (the scratch no longer holds a mask tile map)
     }
     if (s.c->rope_scratch_bytes < (size_t) D * 4 || !attn_one_sm_ok(a)) return false;
     s.pq.fa = m1; s.pq.sm = true; s.pq.kst = B->store; s.pq.vst = vsj; s.pq.sm_soft = smi; s.pq.sm_mm2 = m2; s.pq.sm_cont = ci;
     return true;
+}
+
+// FLASH_ATTN_EXT at node i: the generic kernel, or -- head size 64 / 128 over an f16 cache -- the fused forms: the q / k / v pre-stage a decode layer deferred to it (s.pq),
+// the one-token kernel on the rope table with its slices left to wo (s.gs), the Q8_K / f16 image of the output for the mat-muls behind it
+void exec_fattn(exec_state & s, int i) {
+    ggml_cgraph * g = s.g;
+    ggml_tensor * n = g->nodes[i];
+    fattn_args f; tdesc m;
+    fill_fattn_args(n, f, m);
+    if ((n->src[0]->ne[0] != 64 && n->src[0]->ne[0] != 128) || n->src[2]->ne[0] != n->src[0]->ne[0] || n->src[1]->type != GGML_TYPE_F16) {      // other head sizes / cache types: the generic kernel, no fused stage
+        prof_scope ps(s, "fattn", 0);
+        flash_attn_ext_f16(f, s.st); ++s.n_kernels;
+        note_write(s, n);
+        return;
+    }
+    const bool with_pre = s.pq.fa == i;
+    if (with_pre) f.pre = &s.pq.pre;
+    // one token over a shallow cache: the latency-optimised kernel (fattn_one.hip) takes the token's (cos, sin) from a table that is
+    // computed once per graph, and leaves the Q8_K image to wo's own prologue
+    bool one = false;
+    if (with_pre && fattn_one_ok(f) && s.c->rope_scratch_bytes >= (size_t) n->src[0]->ne[0] * 4) {
+        const fattn_pre & P = s.pq.pre;
+        const int D = (int) n->src[0]->ne[0];
+        f.rope_tab = ensure_rope_table(s, P.pos, P.ff, P.rp, 1, D);
+        one = true;
+        // ... as one workgroup per (KV head, 64-row slice) when the ONE reader of the rows is the next launching node, a batch-1 K-quant mat-vec the LDS-DMA engine
+        // takes (wo): the slices' partial states stay in fa_scratch and that launch folds them in its prologue (mv1_source) -- the f32 rows are never written
+        const int u = s.c->opt_fusion && !is_out(s, n) ? sole_user(s, n) : -1;        // (option "fattn_gs" / MI355X_FA_NO_GS: inside fattn_gs_ok)
+        if (u > i && next_real_node(s, i) == u && fattn_gs_ok(f) && s.c->fa_scratch && s.c->fa_scratch_bytes >= fattn_gs_parts_bytes((int) n->ne[1], D) && mmv2_enabled()) {
+            const ggml_tensor * c = g->nodes[u];
+            const ggml_tensor * x = c->op == GGML_OP_MUL_MAT ? c->src[1] : nullptr;
+            if (x && x->data == n->data && x->ne[0] == n->ne[0] * n->ne[1] && x->ne[1] == 1 && x->ne[2] == 1 && x->ne[3] == 1 && x != s.pn.m && mv1_node_ok(s, c)) {                 // (K-quant or Q8_0 wo: mmv2_ok decides)
+                mv1_args t; t.nmat = 1; t.K = x->ne[0];
+                t.m[0] = { c->src[0]->data, c->src[0]->nb[1], (float *) c->data, 0, nullptr, 0, c->src[0]->ne[1], (int) c->src[0]->type };
+                t.parts = (const float *) s.c->fa_scratch; t.nslice = fattn_gs_nslice();      // (asked, not taken)
+                if (mmv2_ok(t)) { f.gs_parts = (float *) fa_scratch_take(s, FA_GS_SLICES); s.gs.n = n; s.gs.consumer = u; s.gs.nh = (int) n->ne[1]; s.gs.D = D; }
+            }
+        }
+    }
+    // epilogue fusion: when the attention output only feeds K-quant mat-vecs (wo), emit its Q8_K image here
+    const ggml_tensor * xuse = nullptr;
+    if (!one && s.c->opt_fusion && n->ne[3] == 1 && n->ne[2] <= 32 && n_users(s, n) > 0 && !is_out(s, n) &&
+        rms_norm_mul_quant_ok(n->ne[0] * n->ne[1]) && fattn_can_emit_image(f)) {
+        bool ok = true;
+        for (int u : s.users[n]) {
+            const ggml_tensor * c = g->nodes[u];
+            const ggml_tensor * x = c->op == GGML_OP_MUL_MAT ? c->src[1] : nullptr;
+            if (!x || !kq_mm_ok(c) || x->data != n->data || x->ne[0] != n->ne[0] * n->ne[1] || x->ne[1] != n->ne[2] ||
+                x->nb[1] != (size_t) x->ne[0] * 4 || (xuse && !same_act(xuse, x))) { ok = false; break; }
+            xuse = x;
+        }
+        if (!ok) xuse = nullptr;
+    }
+    if (xuse) f.img = act_begin(s);
+    // prefill: the attention output [D, H, nq, ns] read as [H*D, nq*ns] rows by wo's GEMM -> emit those rows in f16 from the kernel
+    const ggml_tensor * xg16 = nullptr;
+    if (!xuse && fattn_uses_mma(f) && n->nb[1] == (size_t) n->ne[0] * 4 && n->nb[2] == (size_t) n->ne[0] * n->ne[1] * 4 &&
+        n->nb[3] == n->nb[2] * (size_t) n->ne[2] && gemm_only_consumers(s, n, n->ne[0] * n->ne[1], n->ne[2] * n->ne[3], &xg16)) {
+        f.out16 = (uint16_t *) act_begin(s); f.out16_rs = act_image_bytes(ACT_F16, n->ne[0] * n->ne[1]); f.write_f32 = n_users(s, n) > 1;
+    }
+    if (fattn_scratch_bytes(f) > 0 && !fattn_uses_mma(f)) {       // decode kernel at long context: workspace of its KV split
+        f.scratch = fa_scratch_take(s, FA_KV_SPLIT, n); f.scratch_bytes = s.c->fa_scratch_bytes;      // (the scratch no longer holds a mask tile map)
+        f.counters = fa_counters(s);
+        ++s.n_kernels;
+    } else if (fattn_scratch_bytes(f) > 0) {
+        // the mask tile map is computed once per mask tensor and graph run (every layer shares the mask)
+        const ggml_tensor * mk = n->src[3];
+        f.scratch = fa_scratch_take(s, FA_MASK_MAP, n); f.scratch_bytes = s.c->fa_scratch_bytes;
+        f.map_valid = s.mask_map.holds(mk, n->src[0]->ne[1]);
+        if (!f.map_valid) { s.mask_map.remember(mk, n->src[0]->ne[1]); ++s.n_kernels; }
+    }
+    {
+        prof_scope ps(s, "fattn", 0);
+        flash_attn_ext_f16(f, s.st); ++s.n_kernels;
+    }
+    note_write(s, n);
+    if (with_pre) { note_write(s, g->nodes[s.pq.kst]); note_write(s, g->nodes[s.pq.vst]); s.pq.fa = -1; }
+    if (xg16) { seed_act_f16(s, xg16); ++s.n_fused; }
+    if (xuse) {
+        s.act.seed(xuse, ACT_Q8K);                                // (2-D: kq_mm_ok)
+        ++s.n_fused;
+    }
+}
+// flash-attention off, one token (s.pq.sm, `i` = the chain's first MUL_MAT): K.q, soft-max, V^T.p, permute + cont and the q / k / v pre-stage in one launch
+void exec_attn_sm_decode(exec_state & s, int) {
+    ggml_cgraph * g = s.g;
+    const fattn_pre & P = s.pq.pre;
+    attn_sm_args & a = s.pq.sma;
+    a.rope_tab = ensure_rope_table(s, P.pos, P.ff, P.rp, 1, a.D);
+    {
+        prof_scope ps(s, "fattn", 0);
+        attn_one_sm(a, s.st); ++s.n_kernels;
+    }
+    s.done[s.pq.sm_soft] = 1; s.done[s.pq.sm_mm2] = 1; s.done[s.pq.sm_cont] = 1; s.n_fused += 3;
+    note_write(s, g->nodes[s.pq.sm_cont]); note_write(s, g->nodes[s.pq.kst]); note_write(s, g->nodes[s.pq.vst]);
+    s.pq.fa = -1; s.pq.sm = false;
 }
 
 // ROPE at node i without a norm in front (llama architecture: the omni TTS decoder, src/llama-model.cpp llm_build_llama): the q chain is
@@ -833,17 +926,8 @@ bool match_rope_only(exec_state & s, int j, nr_chain & c) {
           (!ff || (ff->type == GGML_TYPE_F32 && ff->nb[0] == 4)))) return false;
     c.norm = -1; c.mul = -1; c.rope = j; c.store = -1; c.wt = nullptr; c.pos = pos; c.ff = ff; c.xin = x; c.first = j;
     c.D = (int) D; c.H = (int) r->ne[1]; c.T = (int) r->ne[2]; c.eps = 0.0f;
-    memset(&c.rp, 0, sizeof(c.rp));
-    c.rp.n_dims = op_param_i32(r, 1); c.rp.mode = mode; c.rp.n_ctx_orig = op_param_i32(r, 4);
-    c.rp.freq_base = op_param_f32(r, 5); c.rp.freq_scale = op_param_f32(r, 6); c.rp.ext_factor = op_param_f32(r, 7);
-    c.rp.attn_factor = op_param_f32(r, 8); c.rp.beta_fast = op_param_f32(r, 9); c.rp.beta_slow = op_param_f32(r, 10);
-    const int si = sole_user(s, r);
-    if (si > j && g->nodes[si]->op == GGML_OP_SET_ROWS && !s.done[si]) {
-        const ggml_tensor * S = g->nodes[si], * V = S->src[0], * idx = S->src[1];
-        if (V && idx && V->data == r->data && V->ne[0] == D * r->ne[1] && V->ne[1] == r->ne[2] && V->ne[2] == 1 && V->ne[3] == 1 &&
-            V->nb[1] == r->nb[2] && r->nb[1] == (size_t) D * 4 && S->type == GGML_TYPE_F16 && S->nb[0] == 2 &&
-            (idx->type == GGML_TYPE_I64 || idx->type == GGML_TYPE_I32) && idx->ne[0] == r->ne[2] && idx->ne[1] == 1 && idx->ne[2] == 1) c.store = si;
-    }
+    c.rp = rope_params_of(r);
+    c.store = rope_store_of(s, j);
     return true;
 }
 bool exec_rope_chain(exec_state & s, int i) {
@@ -1028,18 +1112,17 @@ bool exec_rms_norm(exec_state & s, int i) {
                     const ggml_tensor * c = u >= 0 ? g->nodes[u] : nullptr;
                     const ggml_tensor * t = c && c->op == GGML_OP_MUL_MAT ? c->src[1] : nullptr;
                     const ggml_tensor * base = t;
-                    while (base && base != rq && (base->op == GGML_OP_RESHAPE || base->op == GGML_OP_VIEW || base->op == GGML_OP_PERMUTE || base->op == GGML_OP_TRANSPOSE)) base = base->src[0];
+                    while (base && base != rq && view_parent(base)) base = view_parent(base);
                     if (t && base == rq && c->src[0] != t && mm_uses_gemm(c) && !exec_attn_sm_prefill(s, u, true) && t->data == rq->data && t->type == GGML_TYPE_F32 && !is_out(s, t) &&
                         t->ne[0] == A.D && t->ne[1] == A.T && t->ne[2] == A.H && t->ne[3] == 1 && t->nb[0] == 4 && t->nb[1] == (size_t) rq->nb[2] &&
                         t->nb[2] == (size_t) rq->nb[1] && act_image_bytes(ACT_F16, A.D) * (size_t) (A.T * A.H) <= s.c->act_scratch_bytes) q16 = t;
                 }
-                if (q16) { a.j[0].y = nullptr; a.j[0].y16 = s.c->act_scratch; a.j[0].y16_rs = (int64_t) act_image_bytes(ACT_F16, A.D); }
+                if (q16) { a.j[0].y = nullptr; a.j[0].y16 = act_begin(s); a.j[0].y16_rs = (int64_t) act_image_bytes(ACT_F16, A.D); }
                 if (A.T >= ROPE_TABLE_MIN_TOKENS && (size_t) A.T * A.D * 4 <= s.c->rope_scratch_bytes) {
                     // prefill: the angles depend on (position, pair) only -- one table per graph instead of sincos per head, layer and chain
                     a.rope_tab = (float *) s.c->rope_scratch;
-                    a.rope_tab_valid = s.rt.pos == A.pos->data && s.rt.ff == (A.ff ? A.ff->data : nullptr) && s.rt.T == A.T && s.rt.D == A.D &&
-                                       memcmp(&s.rt.rp, &A.rp, sizeof(rope_params)) == 0;
-                    if (!a.rope_tab_valid) { rt_remember(s, A.pos->data, A.ff ? A.ff->data : nullptr, A.T, A.D, A.rp); ++s.n_kernels; }
+                    a.rope_tab_valid = s.rt.holds(A.pos->data, A.ff ? A.ff->data : nullptr, A.T, A.D, A.rp);
+                    if (!a.rope_tab_valid) { s.rt.remember(A.pos->data, A.ff ? A.ff->data : nullptr, A.T, A.D, A.rp); ++s.n_kernels; }
                 }
                 if (s.prm.n) {
                     // every job of this launch reads one of the pending results whole, each result once: point the jobs at the slabs; anything else gets the reduction launch
@@ -1065,9 +1148,7 @@ bool exec_rms_norm(exec_state & s, int i) {
                 if (bj >= 0) note_write(s, g->nodes[B.store >= 0 ? B.store : B.rope]);
                 if (vj >= 0) note_write(s, g->nodes[vj]);
                 if (q16) {                                              // the image of the permuted view [D, T, H] now sits in act_scratch (rows h * T + t)
-                    s.a_src = q16->data; s.a_kind = ACT_F16; s.a_K = q16->ne[0]; s.a_ne[0] = q16->ne[1]; s.a_ne[1] = q16->ne[2]; s.a_ne[2] = q16->ne[3];
-                    s.a_nb[0] = q16->nb[1]; s.a_nb[1] = q16->nb[2]; s.a_nb[2] = q16->nb[3];
-                    s.a_range_lo = (const char *) q16->data; s.a_range_hi = (const char *) q16->data + nbytes(q16);
+                    s.act.seed(q16, ACT_F16);
                     ++s.n_fused;
                 }
                 return true;
@@ -1093,7 +1174,7 @@ bool exec_rms_norm(exec_state & s, int i) {
                 if (s.pn.m) materialise_norm(s);
                 s.done[mi_] = 1; s.n_fused += 2;
                 s.pn.m = m; s.pn.x = xs; s.pn.wt = wt; s.pn.eps = eps; s.pn.left = n_users(s, m);
-                if (s.a_src == m->data) s.a_src = nullptr;
+                if (s.act.src == m->data) s.act.drop();
                 return true;
             }
         }
@@ -1135,7 +1216,7 @@ bool exec_rms_norm(exec_state & s, int i) {
         s.done[mi_] = 1; s.n_fused += 1;
         s.pn.m = m; s.pn.x = xs; s.pn.wt = wt; s.pn.eps = eps; s.pn.left = n_users(s, m);
         if (!defer) { note_write(s, m); materialise_norm(s); }
-        else { ++s.n_fused; if (s.a_src == m->data) s.a_src = nullptr; }
+        else { ++s.n_fused; if (s.act.src == m->data) s.act.drop(); }
         return true;
     }
     const tdesc wd = td(wt);
@@ -1145,18 +1226,19 @@ bool exec_rms_norm(exec_state & s, int i) {
     const bool from_split = s.pr.A && s.pr.A == n->src[0];
     if (from_split && !(n->ne[2] == 1 && n->ne[3] == 1 && wt->ne[0] == n->ne[0] && wt->ne[1] * wt->ne[2] * wt->ne[3] == 1 && m->nb[1] % 16 == 0 && ((uintptr_t) wt->data & 15) == 0))
         materialise_reduce(s);
+    uint16_t * const img16 = emit16 ? (uint16_t *) act_begin(s) : nullptr;
     if (s.pr.A && s.pr.A == n->src[0]) {
         // the norm's input still lies as split-K slabs: reduce, add the residual, write it, and normalise in one pass
         const ggml_tensor * A = s.pr.A;
         const bool w32 = !emit16 || n_users(s, m) > 1;
         prof_scope ps(s, "rms_norm_mul", 0);
         gemm_reduce_rms_norm((const float *) s.c->gemm_partial, s.pr.nsplit, s.pr.resid, s.pr.resid_cs, (float *) A->data, A->nb[1], (const float *) wt->data, eps,
-                             w32 ? (float *) m->data : nullptr, m->nb[1], emit16 ? (uint16_t *) s.c->act_scratch : nullptr, act_image_bytes(ACT_F16, m->ne[0]),
+                             w32 ? (float *) m->data : nullptr, m->nb[1], img16, act_image_bytes(ACT_F16, m->ne[0]),
                              A->ne[0], A->ne[1], s.st, q8);
         s.pr.A = nullptr; ++s.n_fused;
     } else {
         prof_scope ps(s, "rms_norm_mul", 0);
-        if (emit16) rms_norm(td(n->src[0]), td(m), eps, &wd, s.st, (uint16_t *) s.c->act_scratch, act_image_bytes(ACT_F16, m->ne[0]), n_users(s, m) > 1, q8);
+        if (emit16) rms_norm(td(n->src[0]), td(m), eps, &wd, s.st, img16, act_image_bytes(ACT_F16, m->ne[0]), n_users(s, m) > 1, q8);
         else        rms_norm(td(n->src[0]), td(m), eps, &wd, s.st);
     }
     ++s.n_kernels; s.n_fused += 1; s.done[mi_] = 1;
@@ -1231,20 +1313,21 @@ bool exec_attn_sm_prefill(exec_state & s, int i, bool dry) {       // dry: would
         m = td(mk);
         const size_t map_b = attn_sm_mask16_off(nq, nkv), m16_b = mk->type == GGML_TYPE_F32 ? (size_t) mk->ne[1] * (size_t) nkv * 2 : 0;
         if (!s.c->fa_scratch || s.c->fa_scratch_bytes < map_b + m16_b) return false;
-        const bool valid = s.fa_mask == mk->data && s.fa_dims[0] == mk->ne[0] && s.fa_dims[1] == nq && s.fa_dims[2] == mk->ne[2] && s.fa_dims[3] == mk->ne[3] && s.fa_mnb1 == mk->nb[1];
+        void * const fa = fa_scratch_take(s, FA_MASK_MAP);
+        const bool valid = s.mask_map.holds(mk, nq);
         if (mk->type == GGML_TYPE_F32) {
             tdesc m16 = m;
-            m16.p = (char *) s.c->fa_scratch + map_b; m16.nb[0] = 2; m16.nb[1] = (size_t) nkv * 2; m16.nb[2] = m16.nb[1] * (size_t) mk->ne[1]; m16.nb[3] = m16.nb[2];
+            m16.p = (char *) fa + map_b; m16.nb[0] = 2; m16.nb[1] = (size_t) nkv * 2; m16.nb[2] = m16.nb[1] * (size_t) mk->ne[1]; m16.nb[3] = m16.nb[2];
             if (!valid) { prof_scope ps(s, "cpy", 0); cpy_strided(m, GGML_TYPE_F32, m16, GGML_TYPE_F16, s.st); ++s.n_kernels; }
             m = m16;
         }
-        f.mask = &m; f.scratch = s.c->fa_scratch; f.scratch_bytes = map_b; f.map_valid = valid;
-        if (!valid) { fa_mask_remember(s, mk, nq); ++s.n_kernels; }
+        f.mask = &m; f.scratch = fa; f.scratch_bytes = map_b; f.map_valid = valid;
+        if (!valid) { s.mask_map.remember(mk, nq); ++s.n_kernels; }
     }
     // the CONT's rows [D * H, nq * ns] read only by GEMMs (wo): emit them in f16 from the kernel
     const ggml_tensor * xg16 = nullptr;
     if (gemm_only_consumers(s, C, D * H, nq * ns, &xg16)) {
-        f.out16 = (uint16_t *) s.c->act_scratch; f.out16_rs = act_image_bytes(ACT_F16, D * H); f.write_f32 = n_users(s, C) > 1;
+        f.out16 = (uint16_t *) act_begin(s); f.out16_rs = act_image_bytes(ACT_F16, D * H); f.write_f32 = n_users(s, C) > 1;
     }
     {
         prof_scope ps(s, "fattn", 0);

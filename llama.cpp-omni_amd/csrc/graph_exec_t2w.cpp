@@ -37,8 +37,7 @@ bool exec_norm_modulate(exec_state & s, int i) {
     norm_mod_match M;
     if (!match_norm_modulate(s, i, M, true)) return false;
     const ggml_tensor * n = s.g->nodes[i];
-    if (s.pr.A) materialise_reduce(s);
-    if (s.prm.n) materialise_group(s);
+    settle(s);
     {
         prof_scope ps(s, "norm", 0);
         norm_rows_f32(td(n->src[0]), td(M.out), op_param_f32(n, 0), (const float *) M.sv->data, (const float *) M.tv->data, nullptr, 0, true, s.st,
@@ -83,9 +82,7 @@ bool exec_gate_norm(exec_state & s, int i) {
     if ((overlap(range_of(a), range_of(y)) && a->data != y->data) || (overlap(range_of(a), range_of(r)) && a->data != r->data) || overlap(range_of(a), range_of(gv))) return false;
     if (overlap(range_of(M.out), range_of(y)) || overlap(range_of(M.out), range_of(r)) || overlap(range_of(M.out), range_of(gv))) return false;
     const ggml_tensor * n = g->nodes[ni];
-    if (s.pr.A) materialise_reduce(s);
-    if (s.prm.n) materialise_group(s);
-    if (s.pn.m && (s.pn.m == y || s.pn.m == r)) materialise_norm(s);
+    settle(s, { y, r });
     {
         prof_scope ps(s, "norm", 0);
         const norm_gate ng = { (const float *) y->data, (const float *) r->data, (const float *) gv->data, gv->ne[2] > 1 ? gv->nb[2] / 4 : 0 };
@@ -147,7 +144,7 @@ bool exec_attn_f32(exec_state & s, int i) {
     const ggml_tensor * out = M2; int ci = -1;
     a.dst = M2->data; a.d_nb_q = M2->nb[1]; a.d_nb_h = M2->nb[2]; a.d_nb_s = 0; a.H = HB;
     if (!is_out(s, M2)) {
-        auto views_back_to = [](const ggml_tensor * w, const ggml_tensor * t) { while (w && w != t) w = (w->op == GGML_OP_RESHAPE || w->op == GGML_OP_VIEW || w->op == GGML_OP_PERMUTE || w->op == GGML_OP_TRANSPOSE) ? w->src[0] : nullptr; return w != nullptr; };
+        auto views_back_to = [](const ggml_tensor * w, const ggml_tensor * t) { while (w && w != t) w = view_parent(w); return w != nullptr; };
         const int cu = sole_user(s, M2);
         if (cu > m2 && !s.done[cu] && g->nodes[cu]->op == GGML_OP_CONT && next_real_node(s, m2) == cu) {
             const ggml_tensor * C = g->nodes[cu], * cs = C->src[0];
@@ -181,9 +178,7 @@ bool exec_attn_f32(exec_state & s, int i) {
         } else { lazy_materialise(s, lv, (int) GGML_OP_MUL_MAT); lv = nullptr; }
     }
     if (overlap(range_of(out), rv)) return no(__LINE__);
-    if (s.pr.A) materialise_reduce(s);
-    if (s.prm.n) materialise_group(s);
-    if (s.pn.m && (s.pn.m == fq || s.pn.m == fk || s.pn.m == fv)) materialise_norm(s);
+    settle(s, { fq, fk, fv });
     {
         prof_scope ps(s, "attn_f32", 4.0 * (double) D * (double) nq * (double) nkv * (double) HB);
         copy_flush(s);
@@ -375,7 +370,7 @@ void lazy_net(exec_state & s, int i) {
     if (s.lazy.empty()) return;
     const ggml_tensor * n = s.g->nodes[i];
     for (int k = 0; k < GGML_MAX_SRC; ++k)
-        for (const ggml_tensor * t = n->src[k]; t; t = (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE) ? t->src[0] : nullptr)
+        for (const ggml_tensor * t = n->src[k]; t; t = view_parent(t))
             if (s.lazy.count(t)) lazy_materialise(s, t, (int) n->op);
     for (auto it = s.lazy.begin(); it != s.lazy.end(); ) {
         if (it->second.deadline > i) { ++it; continue; }
@@ -387,7 +382,7 @@ void lazy_net(exec_state & s, int i) {
     }
     // a copy made real here was QUEUED (copy_queue): node i is about to launch a kernel that reads it -- or that writes over its source (the deadline) -- unless it is itself a
     // plain copy, whose own job is checked against the queue
-    if (n->op != GGML_OP_CONT && n->op != GGML_OP_CONCAT && n->op != GGML_OP_CPY && n->op != GGML_OP_DUP) copy_flush(s);
+    if (!is_plain_copy(n->op)) copy_flush(s);
 }
 bool lazy_try_register(exec_state & s, int i) {
     static const bool off = getenv("MI355X_NO_LAZY_CACHE_CONT") != nullptr;
@@ -635,9 +630,7 @@ bool exec_causal_conv(exec_state & s, int i) {
     float * wrows = (float *) shadow_get_or_create(s.c->device, Wk->data, nbytes(Wk), /*type: conv rows*/ 1000 + (int) KW, 2 * KW * C, Cout, (size_t) KW * 4, s.st, s.capturing, &created);
     if (!wrows) return no(__LINE__);
     copy_flush(s);                                                      // (copies met but not launched yet: this pattern's kernels read what they write)
-    if (s.pr.A) materialise_reduce(s);
-    if (s.prm.n) materialise_group(s);
-    if (s.pn.m && (s.pn.m == x || s.pn.m == cc)) materialise_norm(s);
+    settle(s, { x, cc });
     if (created) {
         prof_scope ps(s, "conv_weight_rows", 0);
         conv1d_weight_rows((const float *) Wk->data, wrows, (int) KW, (int) C, (int) Cout, s.st); ++s.n_kernels;
@@ -657,7 +650,7 @@ bool exec_causal_conv(exec_state & s, int i) {
         a.X = xbuf->data; a.x_rs = (size_t) C * 4; a.x_nb2 = (size_t) C * (size_t) (T + P) * 4;
         a.dst = (float *) out->data; a.dst_cs = out->nb[1]; a.dst_nb2 = out->nb[2]; a.bias = bias;
         a.M = Cout; a.N = T; a.K = KW * C; a.nbatch = (int) B; a.ne12 = (int) B; a.r2 = (int) B; a.r3 = 1;
-        if (s.c->gemm_partial && s.c->fa_counters) { a.partial = (float *) s.c->gemm_partial; a.partial_bytes = s.c->gemm_partial_bytes; a.counters = s.c->fa_counters; a.n_counters = 1024; }
+        if (s.c->gemm_partial && s.c->fa_counters) { a.partial = (float *) gemm_partial_take(s); a.partial_bytes = s.c->gemm_partial_bytes; a.counters = s.c->fa_counters; a.n_counters = 1024; }
         prof_scope ps(s, "gemm_any_f32", 2.0 * (double) Cout * (double) T * (double) (KW * C) * (double) B);
         gemm_any(a, s.st); ++s.n_kernels;
     }
@@ -707,12 +700,10 @@ bool exec_concat_tail(exec_state & s, int i) {
     if (overlap(range_of(n3), range_of(x))) return false;                           // the copy's buffer was placed for a point of the graph where x may be dead
     // x itself (or what it is a view of) may be a copy that was left un-run (lazy_try_register accepts a CONCAT reader in either operand position): this matcher reads
     // x->data directly and runs BEFORE lazy_net -- make such a copy real first
-    for (const ggml_tensor * t = x; t; t = (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE) ? t->src[0] : nullptr)
+    for (const ggml_tensor * t = x; t; t = view_parent(t))
         if (s.lazy.count(t)) lazy_materialise(s, t, (int) GGML_OP_CONCAT);
     if (s.pr.A || s.prm.n || (s.pn.m && s.pn.m == x)) copy_flush(s);
-    if (s.pr.A) materialise_reduce(s);
-    if (s.prm.n) materialise_group(s);
-    if (s.pn.m && s.pn.m == x) materialise_norm(s);
+    settle(s, { x });
     {
         prof_scope ps(s, "cpy", 0);
         tdesc src = td(x);
@@ -806,9 +797,7 @@ bool exec_conv1d_tc(exec_state & s, int i) {
     bool created = false;
     float * wt = (float *) shadow_get_or_create(s.c->device, Wk->data, nbytes(Wk), /*type: transposed conv kernel*/ 2000, 2 * KW * Cin, Cout, (size_t) KW * 4 + 1, s.st, s.capturing, &created);
     if (!wt) return false;
-    if (s.pr.A) materialise_reduce(s);
-    if (s.prm.n) materialise_group(s);
-    if (s.pn.m && s.pn.m == x) materialise_norm(s);
+    settle(s, { x });
     if (created) {
         prof_scope ps(s, "conv_weight_rows", 0);
         conv1d_weight_t((const float *) Wk->data, wt, (int) (KW * Cin), (int) Cout, s.st); ++s.n_kernels;

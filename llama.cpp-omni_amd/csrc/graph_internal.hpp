@@ -12,7 +12,6 @@
 
 namespace mi {
 
-
 // ------------------------------------------------------------------------------------------------ helpers
 static inline tdesc td(const ggml_tensor * t) {
     tdesc d; d.p = t->data;
@@ -23,6 +22,15 @@ static inline bool is_noop(const ggml_tensor * t) {
     return t->op == GGML_OP_NONE || t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE ||
            t->op == GGML_OP_TRANSPOSE || is_empty(t);
 }
+// one step down a view chain: what a RESHAPE / VIEW / PERMUTE / TRANSPOSE node looks at (null: t is no such node)
+static inline const ggml_tensor * view_parent(const ggml_tensor * t) {
+    return (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE) ? t->src[0] : nullptr;
+}
+// the ops whose launch is one strided copy: they may join the copy queue instead of flushing it
+static inline bool is_plain_copy(int op) { return op == GGML_OP_CONT || op == GGML_OP_CONCAT || op == GGML_OP_CPY || op == GGML_OP_DUP; }
+struct byte_range { const char * lo; const char * hi; };
+static inline byte_range range_of(const ggml_tensor * t) { const char * p = (const char *) t->data; return { p, p + nbytes(t) }; }
+static inline bool overlap(byte_range a, byte_range b) { return a.lo < b.hi && b.lo < a.hi && a.lo != a.hi && b.lo != b.hi; }
 
 enum act_kind { ACT_NONE = 0, ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32, ACT_Q8KT, ACT_F16Q };      // F16Q: f16 rows of the Q8_K-quantised values (what the F16-image GEMMs of K-quant weights multiply with)      // Q8KT: the block-major Q8_K image of a whole ubatch (mmq_tile.hip), not a per-row format
 // block formats without integer-dot kernels of their own: every MUL_MAT runs on the F16 image of the weights (resident for model
@@ -54,6 +62,42 @@ static inline size_t act_image_bytes(act_kind k, int64_t K) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ state the executor carries from one node to a later one
+// Each piece says once: where it lives, who sets it, who consumes it, what ends it.  All of it dies with the exec_state (one per graph_compute).
+// The three CACHES own their key AND the bytes they were computed from: note_write passes every written range to invalidate(); one that does not hold() costs a launch.
+// act -- in act_scratch: x's rows in the format `kind`, row r of the flattened [ne1 * ne2 * ne3] at r * act_image_bytes(kind, K).  Set by seed(): prepare_act, and every
+//   producer that writes its result's image in its own launch (materialise_norm, SWIGLU, SOFT_MAX, the gathering CONT, the attention launches; through seed_act_f16: UNARY,
+//   GLU, the norms, the GEMM epilogues).  Consumed by prepare_act, op_mul_mat's any-shape GEMM, mv1_source.  Ended by act_begin() -- where every writer of the scratch gets
+//   the pointer, so one that forgets to seed leaves no record -- and by a write into x.
+struct act_cache {
+    const void * src = nullptr; act_kind kind = ACT_NONE; int64_t K = 0, ne[3] = { 0, 0, 0 }; size_t nb[3] = { 0, 0, 0 }; byte_range from = { nullptr, nullptr };
+    bool holds(const ggml_tensor * x, act_kind k) const { return holds_row(x, k, x->ne[1]) && nb[0] == x->nb[1] && nb[1] == x->nb[2] && nb[2] == x->nb[3]; }
+    // mv1_source's batch-1 mat-vecs ([K, 1, 1, 1] at every caller): one row, whose strides address nothing (a one-row view carries its parent's) -- left out
+    bool holds_row(const ggml_tensor * x, act_kind k, int64_t rows = 1) const { return src == x->data && kind == k && K == x->ne[0] && ne[0] == rows && ne[1] == x->ne[2] && ne[2] == x->ne[3]; }
+    void seed(const ggml_tensor * x, act_kind k) { src = x->data; kind = k; K = x->ne[0]; from = range_of(x); for (int d = 0; d < 3; ++d) { ne[d] = x->ne[d + 1]; nb[d] = x->nb[d + 1]; } }
+    void drop() { src = nullptr; }      void invalidate(byte_range w) { if (src && overlap(w, from)) drop(); }
+};
+// rt -- in rope_scratch: the (cos, sin) table of T positions x D / 2 pairs.  Set by remember(): ensure_rope_table (the one-token attention launches) and the prefill
+//   norm + rope launch, which fills the table itself when told it is not valid.  Consumed by the same (every layer of a graph shares it).  Ended by a write into the
+//   positions or frequency factors read.
+struct rope_cache {
+    const void * pos = nullptr; const void * ff = nullptr; int T = 0, D = 0; rope_params rp; byte_range from_pos = { nullptr, nullptr }, from_ff = { nullptr, nullptr };
+    bool holds(const void * p, const void * f, int T_, int D_, const rope_params & r) const { return pos && pos == p && ff == f && T == T_ && D == D_ && memcmp(&rp, &r, sizeof(rope_params)) == 0; }
+    void remember(const void * p, const void * f, int T_, int D_, const rope_params & r) {      // T positions and D / 2 frequency factors were read
+        pos = p; ff = f; T = T_; D = D_; rp = r; from_pos = { (const char *) p, (const char *) p + (size_t) T_ * 4 }; from_ff = { (const char *) f, f ? (const char *) f + (size_t) (D_ / 2) * 4 : nullptr };
+    }
+    void drop() { pos = nullptr; }      void invalidate(byte_range w) { if (pos && (overlap(w, from_pos) || overlap(w, from_ff))) drop(); }
+};
+// mask_map -- at the head of fa_scratch: the tile map of mask `mk` against nq query rows (flash-attention off: an f32 mask's f16 copy behind it).  Set by remember(): the
+//   prefill attention launches (exec_fattn on the MFMA kernel, exec_attn_sm_prefill), which compute the map when told it is not valid.  Consumed by the same.  Ended by
+//   a write into the mask, and by any other tenant taking the scratch (fa_scratch_take).
+struct mask_map_cache {
+    const void * mask = nullptr; int64_t ne[4] = { 0, 0, 0, 0 }; size_t nb1 = 0; byte_range from = { nullptr, nullptr };
+    bool holds(const ggml_tensor * mk, int64_t nq) const { return mask && mask == mk->data && ne[0] == mk->ne[0] && ne[1] == nq && ne[2] == mk->ne[2] && ne[3] == mk->ne[3] && nb1 == mk->nb[1]; }
+    void remember(const ggml_tensor * mk, int64_t nq) { mask = mk->data; ne[0] = mk->ne[0]; ne[1] = nq; ne[2] = mk->ne[2]; ne[3] = mk->ne[3]; nb1 = mk->nb[1]; from = range_of(mk); }
+    void drop() { mask = nullptr; }      void invalidate(byte_range w) { if (mask && overlap(w, from)) drop(); }
+};
+
 struct exec_state {
     backend_ctx * c;
     hipStream_t   st;
@@ -63,37 +107,35 @@ struct exec_state {
     std::unordered_map<const ggml_tensor *, int> index;                  // tensor -> node index
     std::unordered_map<const ggml_tensor *, std::vector<int>> users;     // tensor -> consumer node indices (ascending)
     std::unordered_set<const ggml_tensor *> external;                    // tensors with readers outside this cgraph (see is_out)
-    const char * a_range_lo = nullptr; const char * a_range_hi = nullptr;
-    // activation cache
-    const void *  a_src = nullptr; act_kind a_kind = ACT_NONE; int64_t a_K = 0, a_ne[3] = {0, 0, 0}; size_t a_nb[3] = {0, 0, 0};
     bool          capturing = false;
     int           node_lo = 0, node_hi = -1;      // run_nodes walks [node_lo, node_hi) (-1: to the end) -- the slice timer of graph_compute (MI355X_GRAPH_SLICE)
-    // deferred RMS_NORM -> MUL(w): not computed yet; its K-quant mat-vec consumers build the Q8_K image in-kernel (mmvk.hip act_norm)
+    act_cache      act;
+    rope_cache     rt;
+    mask_map_cache mask_map;
+    // DEFERRED work: a node that did not launch, or whose result is not in its tensor yet.
+    // pn -- nowhere yet: RMS_NORM -> MUL(w) = `m`, not computed.  Set by exec_rms_norm.  Consumed by the K-quant / Q8_0 mat-vecs that build the image of m in-kernel
+    //   (norm_in_kernel, mv1_source; `left` readers to go).  Ended by the last of them, or by materialise_norm for any other reader (prepare_act, op_mul_mat, settle).
     struct { const ggml_tensor * m = nullptr; const ggml_tensor * x = nullptr; const ggml_tensor * wt = nullptr; float eps = 0; int left = 0; } pn;
-    // deferred q chain + k chain/store + v store of a decode layer: executed by the FLASH_ATTN_EXT node `fa` itself (fattn_pre)
+    // pq -- nowhere yet: the q chain, k chain + store and v store of a decode layer.  Set by try_defer_qkv_to_attention / _to_softmax_attention (`sm`: the flash-attention-off
+    //   form, `fa` = its first MUL_MAT).  Consumed and ended by the attention node `fa`, which runs them in its own launch (exec_fattn / exec_attn_sm_decode).
     struct { int fa = -1; fattn_pre pre; int kst = -1, vst = -1;
-             bool sm = false; int sm_soft = -1, sm_mm2 = -1, sm_cont = -1; attn_sm_args sma; } pq;   // sm: the flash-attention-off form, `fa` = its first MUL_MAT
-    // deferred split-K reduction: `A` (the mat-mul + residual result) still lies as `nsplit` slabs in gemm_partial; the RMS_NORM that
-    // reads it next folds the reduction in (gemm_reduce_rms_norm), anything else materialises it first
-    struct { const ggml_tensor * A = nullptr; int nsplit = 0; const float * resid = nullptr; size_t resid_cs = 0; const float * resid2 = nullptr; size_t resid2_cs = 0; } pr;   // (resid2: only in front of a LayerNorm)
-    // one-token attention left as slices' partial states in fa_scratch (fattn_one.hip k_fattn_gs): `n` = the FLASH_ATTN_EXT node whose f32 rows were NOT written, `consumer` = the
-    // one MUL_MAT (wo) that folds them in its prologue (mv1_source); anything else that runs first materialises the rows (gs_materialise in graph_exec.cpp)
-    struct { const ggml_tensor * n = nullptr; int consumer = -1; int nh = 0, D = 0; } gs;
-    // (pos, rope parameters) whose (cos, sin) table currently sits in rope_scratch (prefill: shared by every layer of the graph); [lo, hi) / [ff_lo, ff_hi): the bytes of
-    // the positions and frequency factors the table was computed from -- a node that writes any of them drops the table (note_write)
-    struct { const void * pos = nullptr; const void * ff = nullptr; int T = 0, D = 0; rope_params rp; const char * lo = nullptr, * hi = nullptr, * ff_lo = nullptr, * ff_hi = nullptr; } rt;
-    // mask whose tile map currently sits in fa_scratch; [fa_mask_lo, fa_mask_hi): the mask's bytes (a write into any row of it drops the map, note_write)
-    const void *  fa_mask = nullptr; int64_t fa_dims[4] = {0, 0, 0, 0}; size_t fa_mnb1 = 0; const char * fa_mask_lo = nullptr, * fa_mask_hi = nullptr;
-    // a V^T that a fused soft-max attention will read where it LIES (a transposed V cache) instead of from the CONT + CAST copies the graph makes of it: `cast` = the CAST node the
-    // attention's second mat-mul names, `v` = the same elements in the cache (try_alias_vt in graph_exec.cpp)
-    struct { const ggml_tensor * cast = nullptr; tdesc v; int cont_i = -1, cast_i = -1; } va;
-    // an encoder's V^T CAST tensor `t` whose bytes were written as V ROWS instead ([D, n_tokens, H] like K: the GEMM epilogue that makes the f16 copy chooses the layout): its one
-    // reader, the flash-attention-off chain exec_attn_sm_prefill fuses, then runs as plain flash attention on the LDS-DMA ring kernel (head size 64); set by exec_gemm_group
-    // once the launch that writes the rows has taken the CAST, cleared by the attention launch that reads them (and at the start of run_nodes) -- nothing else
-    struct { const ggml_tensor * t = nullptr; tdesc v; } vplain;
-    // deferred split-K reduction of a GROUPED launch (wq / wk / wv of a prefill ubatch): the results A[0..n) still lie as `nsplit` slabs in gemm_partial (slab = `slab` floats,
-    // matrix q a dense [N][M[q]] block at + off[q]); the q / k norm + rope + store launch behind them sums the slabs itself (k_norm_rope_v4), anybody else gets materialise_group
+             bool sm = false; int sm_soft = -1, sm_mm2 = -1, sm_cont = -1; attn_sm_args sma; } pq;
+    // pr -- in gemm_partial: `A` (a mat-mul + residual result; resid2 only in front of a LayerNorm) as `nsplit` split-K slabs.  Set by exec_gemm_group.  Consumed by the
+    //   (RMS_)NORM that reads A next and sums the slabs itself (exec_rms_norm, exec_norm).  Ended by that launch, or by materialise_reduce for anybody else (settle).
+    struct { const ggml_tensor * A = nullptr; int nsplit = 0; const float * resid = nullptr; size_t resid_cs = 0; const float * resid2 = nullptr; size_t resid2_cs = 0; } pr;
+    // prm -- in gemm_partial: the results A[0..n) of a GROUPED launch (wq / wk / wv of a prefill ubatch) as `nsplit` slabs of `slab` floats, matrix q a dense [N][M[q]] block
+    //   at + off[q].  Set by exec_gemm_group.  Consumed by the q / k norm + rope + store launch behind it (exec_rms_norm).  Ended by it, or by materialise_group (settle).
     struct { int n = 0; const ggml_tensor * A[3] = { nullptr, nullptr, nullptr }; size_t off[3] = { 0, 0, 0 }; int64_t M[3] = { 0, 0, 0 }; int nsplit = 0; size_t slab = 0; int64_t N = 0; } prm;
+    // gs -- in fa_scratch: one-token attention as slices' partial states (k_fattn_gs); the f32 rows of the FLASH_ATTN_EXT node `n` were NOT written.  Set by exec_fattn.
+    //   Consumed by `consumer`, the one MUL_MAT (wo) that folds them in its prologue (mv1_source).  Ended by it, or by gs_materialise when anything else runs first (run_nodes).
+    struct { const ggml_tensor * n = nullptr; int consumer = -1; int nh = 0, D = 0; } gs;
+    // va -- in a transposed V cache: the V^T a fused soft-max attention reads where it LIES instead of from the CONT + CAST copies the graph makes (`cast` = the CAST its second
+    //   mat-mul names, `v` = the same elements in the cache).  Set by try_alias_vt.  Consumed and ended by exec_attn_sm_prefill; materialise_vt runs the copies otherwise.
+    struct { const ggml_tensor * cast = nullptr; tdesc v; int cont_i = -1, cast_i = -1; } va;
+    // vplain -- in the V^T CAST tensor `t` of an encoder: its bytes written as V ROWS ([D, n_tokens, H], like K).  Set by exec_gemm_group once the launch that writes the rows
+    //   has taken the CAST.  Consumed and ended by its one reader, the chain exec_attn_sm_prefill runs as plain flash attention (head size 64) -- and by nothing else but the
+    //   start of run_nodes.
+    struct { const ggml_tensor * t = nullptr; tdesc v; } vplain;
     // CONT nodes that have NOT been run: copies of a view of a tensor from outside the graph (a persistent cache) whose readers may take the view itself (lazy_* in
     // graph_exec.cpp).  `src` = what the copy would read, `deadline` = the first node that writes over those bytes; any other reader materialises the copy first.
     struct lazy_ent { tdesc src; int deadline; };

@@ -1,7 +1,7 @@
 """The executor's deferred and cached state against in-graph writes (graph_internal.hpp exec_state).
 
 graph_exec*.cpp carries state from one node to a later one: the V-rows layout of an encoder's V^T CAST (vplain), the copy queue (cq) and the Token2Wav concat tail,
-the RoPE table (rt), the mask tile map (fa_mask), the activation image (a_src), the deferred RMS_NORM (pn), the split-K reductions (pr) and the lazy copies (lazy).
+the RoPE table (rt), the mask tile map (mask_map), the activation image (act), the deferred RMS_NORM (pn), the split-K reductions (pr) and the lazy copies (lazy).
 Each is valid only until a node writes the bytes it depends on.  Every case here is a PAIR of small graphs in an explicit node order (Context.graph(), not
 graph_expand): a control that takes the fused path -- proved by a launch count below the fusion-off run or by a named counter -- and the same graph with one legal
 node that writes those bytes in between (a CPY into a view: how ggml writes in place).  Each graph runs on the backend with its defaults (eager, captured, replayed:
@@ -178,7 +178,7 @@ def test_rope_table_is_recomputed_after_a_write_to_the_positions(pkg, be, ref_be
     assert k_on < k_off, (k_on, k_off)                                  # norm + mul + rope: one launch per chain (or both in one)
 
 
-# ------------------------------------------------------------------------------------------------ fa_mask
+# ------------------------------------------------------------------------------------------------ mask_map
 # Two prefill FLASH_ATTN_EXT nodes sharing an F16 mask (the matrix-core kernel with the mask tile map computed once per mask and graph run).  Interloper: a CPY of new rows into
 # rows 32..63 of the mask between them; control: a CPY over the whole mask.  The new rows mask every key from 16 on where the old ones masked nothing.  Bar: 5e-4 NMSE, the
 # reference's FLASH_ATTN_EXT bar (test_gpu_parity.py test_flash_attn_prefill_mfma).
@@ -211,7 +211,7 @@ def test_mask_tile_map_is_recomputed_after_a_write_into_the_mask(pkg, be, ref_be
     assert k_on < k_off, (k_on, k_off)                                  # the copy queued instead of launched on its own
 
 
-# ------------------------------------------------------------------------------------------------ a_src
+# ------------------------------------------------------------------------------------------------ act
 # MUL_MAT(W1, x), a CPY into one column of x, MUL_MAT(W2, x): the second product must not take the activation image the first one left.  Q4_K weights at 4 columns (the MMVQ
 # mat-vec on the Q8_K image), Q8_0 weights at one column (the batch-1 mv1 form).  Bar: 5e-4 NMSE, the reference's MUL_MAT bar.
 @pytest.mark.parametrize("wtype,N", [("q4_K", 4), ("q8_0", 1)])
