@@ -46,11 +46,6 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
     return img;
 }
 
-const char * mmv_class(int type) {
-    return type == GGML_TYPE_Q4_K ? "mmv_q4k" : type == GGML_TYPE_Q6_K ? "mmv_q6k" : type == GGML_TYPE_Q8_0 ? "mmv_q80" : type == GGML_TYPE_F16 ? "mmv_f16" :
-           type == GGML_TYPE_IQ4_NL ? "mmv_iq4nl" : type == GGML_TYPE_IQ4_XS ? "mmv_iq4xs" : "mmv_f32";
-}
-
 // resident F16 image of a quantised weight matrix (shadow.hpp): built on first use outside of graph capture, only for tensors
 // that live in a buffer marked GGML_BACKEND_BUFFER_USAGE_WEIGHTS
 const uint16_t * weight_shadow(exec_state & s, const ggml_tensor * w, const char * wp, int64_t K, int64_t M) {
@@ -68,170 +63,161 @@ const uint16_t * weight_shadow(exec_state & s, const ggml_tensor * w, const char
     return p;
 }
 
-// does op_mul_mat send this MUL_MAT to the any-shape GEMM (gemm_any.hip)?  (after the MFMA GEMM and BF16 branches)
-bool mm_takes_gemm_any(const ggml_tensor * n) {
-    static const bool no_gemm_any = getenv("MI355X_NO_GEMM_ANY") != nullptr;
-    const ggml_tensor * w = n->src[0], * x = n->src[1];
+// ---- MUL_MAT: one function per path of route_mul_mat (graph_plan.cpp), which alone decides between them
+static void mm_mmq_tile(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // Q4_K x a prefill ubatch: the tiled int8-MFMA kernel on the Q8_K image (mmq_tile.hip)
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
     const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1];
-    if (no_gemm_any || mm_uses_gemm(n) || w->type == GGML_TYPE_BF16) return false;
-    return (w->type == GGML_TYPE_F32 || w->type == GGML_TYPE_F16) && N > MI_MMVQ_MAX_COLS &&
-           ((x->type == GGML_TYPE_F32 && x->nb[0] == 4) || (x->type == GGML_TYPE_F16 && x->nb[0] == 2 && w->type == GGML_TYPE_F16)) && w->nb[0] == (w->type == GGML_TYPE_F16 ? 2u : 4u) && n->nb[0] == 4 &&
-           x->ne[2] * x->ne[3] <= 65535 && M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31);
+    prepare_act(s, x, r.act);
+    mmqt_args q;
+    q.nmat = 1; q.m[0] = { w->data, w->nb[1], (float *) dst->data, dst->nb[1], M }; q.img = s.c->act_scratch; q.N = N; q.K = K;
+    if (dst->nb[1] % 16 == 0 && gemm_split_scratch_bytes(M, N, K) <= s.c->gemm_partial_bytes) { q.partial = (float *) gemm_partial_take(s); q.partial_bytes = s.c->gemm_partial_bytes; }
+    prof_scope ps(s, "mmq_tile", 2.0 * (double) M * (double) N * (double) K);
+    mmq_tile(q, s.st);
+    ++s.n_kernels;
 }
-void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out, const float * bias, const mm_sibling * sib, int nsib, bool * sib_taken, int act) {
-    const ggml_tensor * w = dst->src[0];
-    const ggml_tensor * x = dst->src[1];
-    if (!out) out = dst;
-    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1];
-    const int64_t ne12 = x->ne[2], ne13 = x->ne[3];
-    const int64_t r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
-
-    if (mm_uses_mmq_tile(dst)) {                                // Q4_K x a prefill ubatch: the tiled int8-MFMA kernel on the Q8_K image (mmq_tile.hip)
-        prepare_act(s, x, ACT_Q8KT);
-        mmqt_args q;
-        q.nmat = 1; q.m[0] = { w->data, w->nb[1], (float *) dst->data, dst->nb[1], M }; q.img = s.c->act_scratch; q.N = N; q.K = K;
-        if (dst->nb[1] % 16 == 0 && gemm_split_scratch_bytes(M, N, K) <= s.c->gemm_partial_bytes) { q.partial = (float *) gemm_partial_take(s); q.partial_bytes = s.c->gemm_partial_bytes; }
-        prof_scope ps(s, "mmq_tile", 2.0 * (double) M * (double) N * (double) K);
-        mmq_tile(q, s.st);
-        ++s.n_kernels;
-        return;
-    }
-    if (mm_uses_gemm(dst)) {
-        // ---- prefill: MFMA GEMM.  X -> f16 rows (what the reference does for F16 weights, ggml-cpu.c:1245-1268); quantised W -> f16
-        const size_t ximg = prepare_act(s, x, x->ne[2] * x->ne[3] == 1 ? gemm_act_kind(dst) : ACT_F16);
-        // attention without FLASH_ATTN_EXT at prefill: every head's K.Q^T (or V^T.P) product in one launch
-        if (w->type == GGML_TYPE_F16 && ne12 * ne13 > 1 && ne12 * ne13 <= 65535 && K % 64 == 0 && w->nb[1] % 16 == 0 && w->nb[2] % 16 == 0 && w->nb[3] % 16 == 0 &&
-            ((uintptr_t) w->data & 15) == 0 && dst->nb[0] == 4) {
-            gemm_multi_args a;
-            a.nmat = 1; a.m[0] = { (const uint16_t *) w->data, w->nb[1], (float *) dst->data, dst->nb[1], M, nullptr, 0 };
-            a.X = (const uint16_t *) s.c->act_scratch; a.x_rs = ximg; a.N = N; a.K = K; a.partial = nullptr;
-            a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
-            a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.x_bs = (size_t) N * ximg; a.dst_nb2 = dst->nb[2]; a.dst_nb3 = dst->nb[3];
-            prof_scope ps(s, "gemm_f16", 2.0 * (double) M * (double) N * (double) K * (double) (ne12 * ne13));
-            gemm_f16_multi(a, s.st);
-            ++s.n_kernels;
-            return;
-        }
-        const void * last_w = nullptr;
-        for (int64_t i13 = 0; i13 < ne13; ++i13) {
-            for (int64_t i12 = 0; i12 < ne12; ++i12) {
-                const char * wp = (const char *) w->data + (i12 / r2) * w->nb[2] + (i13 / r3) * w->nb[3];
-                const uint16_t * w16 = (const uint16_t *) wp; size_t w16_rs = w->nb[1];
-                const uint16_t * sh = w->type != GGML_TYPE_F16 ? weight_shadow(s, w, wp, K, M) : nullptr;
-                if (sh) { w16 = sh; w16_rs = (size_t) K * 2; }
-                else if (w->type != GGML_TYPE_F16) {
-                    if (wp != last_w) {
-                        prof_scope ps(s, "dequant_f16", (double) M * (double) row_size(w->type, K));
-                        dequant_rows_f16(w->type, wp, w->nb[1], (uint16_t *) s.c->w_scratch, (size_t) K * 2, K, M, s.st); ++s.n_kernels;
-                        last_w = wp;
-                    }
-                    w16 = (const uint16_t *) s.c->w_scratch; w16_rs = (size_t) K * 2;
+static void mm_gemm_f16_heads(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // attention without FLASH_ATTN_EXT at prefill: every head's K.Q^T (or V^T.P) product in one launch
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const size_t ximg = prepare_act(s, x, r.act);
+    gemm_multi_args a;
+    a.nmat = 1; a.m[0] = { (const uint16_t *) w->data, w->nb[1], (float *) dst->data, dst->nb[1], M, nullptr, 0 };
+    a.X = (const uint16_t *) s.c->act_scratch; a.x_rs = ximg; a.N = N; a.K = K; a.partial = nullptr;
+    a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
+    a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.x_bs = (size_t) N * ximg; a.dst_nb2 = dst->nb[2]; a.dst_nb3 = dst->nb[3];
+    prof_scope ps(s, "gemm_f16", 2.0 * (double) M * (double) N * (double) K * (double) (ne12 * ne13));
+    gemm_f16_multi(a, s.st);
+    ++s.n_kernels;
+}
+static void mm_gemm_f16(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // the MFMA GEMM, slice by slice; quantised W through its F16 image
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const size_t ximg = prepare_act(s, x, r.act);
+    const void * last_w = nullptr;
+    for (int64_t i13 = 0; i13 < ne13; ++i13) {
+        for (int64_t i12 = 0; i12 < ne12; ++i12) {
+            const char * wp = (const char *) w->data + (i12 / r2) * w->nb[2] + (i13 / r3) * w->nb[3];
+            const uint16_t * w16 = (const uint16_t *) wp; size_t w16_rs = w->nb[1];
+            const uint16_t * sh = r.w_image ? weight_shadow(s, w, wp, K, M) : nullptr;
+            if (sh) { w16 = sh; w16_rs = (size_t) K * 2; }
+            else if (r.w_image) {
+                if (wp != last_w) {
+                    prof_scope ps(s, "dequant_f16", (double) M * (double) row_size(w->type, K));
+                    dequant_rows_f16(w->type, wp, w->nb[1], (uint16_t *) s.c->w_scratch, (size_t) K * 2, K, M, s.st); ++s.n_kernels;
+                    last_w = wp;
                 }
-                const char * xp = (const char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N) * ximg;
-                prof_scope ps(s, "gemm_f16", 2.0 * (double) M * (double) N * (double) K);
-                gemm_f16_mfma(w16, w16_rs, (const uint16_t *) xp, ximg, (float *) ((char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]), dst->nb[1], M, N, K, s.st);
-                ++s.n_kernels;
+                w16 = (const uint16_t *) s.c->w_scratch; w16_rs = (size_t) K * 2;
             }
-        }
-        return;
-    }
-
-    if (w->type == GGML_TYPE_BF16) {
-        if (s.pn.m && x == s.pn.m) materialise_norm(s);
-        gemm_any_args a;
-        a.W = w->data; a.w_rs = w->nb[1]; a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.w_f16 = false; a.w_bf16 = true;
-        a.X = x->data; a.x_rs = x->nb[1]; a.x_nb2 = x->nb[2]; a.x_nb3 = x->nb[3];
-        a.dst = (float *) dst->data; a.dst_cs = dst->nb[1]; a.dst_nb2 = dst->nb[2]; a.dst_nb3 = dst->nb[3];
-        a.M = M; a.N = N; a.K = K; a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
-        prof_scope ps(s, "gemm_any_bf16", 2.0 * (double) M * (double) N * (double) K * (double) (ne12 * ne13));
-        gemm_any(a, s.st);
-        ++s.n_kernels;
-        return;
-    }
-    const act_kind kind = act_kind_for(w->type);
-    // more than 8 columns against F32 weights, or F16 weights with a contraction length the F16 GEMM does not take (the omni encoders, Token2Wav):
-    // one f32-MFMA launch over every (head, batch) instead of a mat-vec launch per 8 columns per head
-    if (mm_takes_gemm_any(dst)) {
-        if (s.pn.m && x == s.pn.m) materialise_norm(s);
-        gemm_any_args a;
-        int64_t k_done = 0;
-        // the producer (SOFT_MAX of an encoder's / a flash-attention-off prefill's scores, or an earlier mat-mul on the same x) left the f16 image of x in
-        // the scratch -- and possibly did not write the f32 block at all
-        bool x_img = w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && s.act.holds(x, ACT_F16);
-        // F16 weights, K a few columns past a multiple of 64 (SigLip2's n_ff 4304): the F16 MFMA GEMM takes the first K - K % 64 columns, this kernel adds the tail
-        if (w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && ne12 * ne13 == 1 && K % 64 != 0 && K >= 512 && w->nb[1] % 16 == 0 && ((uintptr_t) w->data & 15) == 0 &&
-            out->nb[1] % 16 == 0 && act_image_bytes(ACT_F16, K) * (size_t) N <= s.c->act_scratch_bytes) {
-            const size_t ximg = prepare_act(s, x, ACT_F16);        // (nothing to do when the image is there already)
-            x_img = true;
-            k_done = K - K % 64;
-            prof_scope ps(s, "gemm_f16", 2.0 * (double) M * (double) N * (double) k_done);
-            gemm_multi_args ga;                                  // (split along K when the tiles do not fill the chip: SigLip2's fc2, 1152 x 1024 outputs, went from 79 to 24 us)
-            ga.nmat = 1; ga.m[0] = { (const uint16_t *) w->data, w->nb[1], (float *) out->data, out->nb[1], M, nullptr, 0 };
-            ga.X = (const uint16_t *) s.c->act_scratch; ga.x_rs = ximg; ga.N = N; ga.K = k_done;
-            ga.partial = gemm_split_scratch_bytes(M, N, k_done) <= s.c->gemm_partial_bytes ? (float *) gemm_partial_take(s) : nullptr; ga.partial_bytes = s.c->gemm_partial_bytes;
-            gemm_f16_multi(ga, s.st);
+            const char * xp = (const char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N) * ximg;
+            prof_scope ps(s, "gemm_f16", 2.0 * (double) M * (double) N * (double) K);
+            gemm_f16_mfma(w16, w16_rs, (const uint16_t *) xp, ximg, (float *) ((char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]), dst->nb[1], M, N, K, s.st);
             ++s.n_kernels;
         }
-        a.W = (const char *) w->data + k_done * (w->type == GGML_TYPE_F16 ? 2 : 4); a.w_rs = w->nb[1]; a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.w_f16 = w->type == GGML_TYPE_F16;
-        if (x_img) {                                             // rows of the image: [ne13][ne12][N] x act_image_bytes
-            const size_t img = act_image_bytes(ACT_F16, K);
-            a.X = (const char *) s.c->act_scratch + k_done * 2; a.x_rs = img; a.x_nb2 = img * (size_t) N; a.x_nb3 = img * (size_t) (N * ne12); a.x_f16 = true;
-        } else {
-            a.X = (const char *) x->data + k_done * (x->type == GGML_TYPE_F16 ? 2 : 4); a.x_rs = x->nb[1]; a.x_nb2 = x->nb[2]; a.x_nb3 = x->nb[3]; a.x_f16 = x->type == GGML_TYPE_F16;
-        }
-        a.dst = (float *) out->data; a.dst_cs = out->nb[1]; a.dst_nb2 = out->nb[2]; a.dst_nb3 = out->nb[3]; a.accumulate = k_done > 0; a.bias = bias; a.act = act;
-        a.M = M; a.N = N; a.K = K - k_done; a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
-        if (s.c->gemm_partial && fa_counters(s)) { a.partial = (float *) gemm_partial_take(s); a.partial_bytes = s.c->gemm_partial_bytes; a.counters = s.c->fa_counters; a.n_counters = 1024; }
-        if (nsib > 0 && sib_taken) {
-            *sib_taken = false;
-            if (k_done == 0 && !x_img && w->type == GGML_TYPE_F32 && x->type == GGML_TYPE_F32) {
-                a.nmat = 1 + nsib;
-                for (int q = 0; q < nsib; ++q) { a.W_more[q] = sib[q].w->data; a.dst_more[q] = (float *) sib[q].out->data; a.bias_more[q] = sib[q].bias; }
-                if (gemm_any_group_ok(a)) *sib_taken = true; else a.nmat = 1;
-            }
-        }
-        prof_scope ps(s, w->type == GGML_TYPE_F16 ? "gemm_any_f16" : "gemm_any_f32", 2.0 * (double) M * (double) N * (double) (K - k_done) * (double) (ne12 * ne13) * (double) a.nmat);
-        gemm_any(a, s.st);
-        ++s.n_kernels;
-        return;
     }
-    const size_t img = prepare_act(s, x, kind);
-
+}
+static void mm_gemm_bf16(exec_state & s, const ggml_tensor * dst) {
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    if (s.pn.m && x == s.pn.m) materialise_norm(s);
+    gemm_any_args a;
+    a.W = w->data; a.w_rs = w->nb[1]; a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.w_f16 = false; a.w_bf16 = true;
+    a.X = x->data; a.x_rs = x->nb[1]; a.x_nb2 = x->nb[2]; a.x_nb3 = x->nb[3];
+    a.dst = (float *) dst->data; a.dst_cs = dst->nb[1]; a.dst_nb2 = dst->nb[2]; a.dst_nb3 = dst->nb[3];
+    a.M = M; a.N = N; a.K = K; a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
+    prof_scope ps(s, "gemm_any_bf16", 2.0 * (double) M * (double) N * (double) K * (double) (ne12 * ne13));
+    gemm_any(a, s.st);
+    ++s.n_kernels;
+}
+void mm_gemm_any(exec_state & s, const ggml_tensor * dst, const mm_route & r, const mm_extras & e) {
+    if (r.path != MM_GEMM_ANY) { fprintf(stderr, "[mi355x] mm_gemm_any: a MUL_MAT the any-shape GEMM does not take\n"); abort(); }
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const ggml_tensor * out = e.out ? e.out : dst;
+    if (s.pn.m && x == s.pn.m) materialise_norm(s);
+    gemm_any_args a;
+    int64_t k_done = 0;
+    // the producer (SOFT_MAX of an encoder's / a flash-attention-off prefill's scores, or an earlier mat-mul on the same x) left the f16 image of x in
+    // the scratch -- and possibly did not write the f32 block at all
+    bool x_img = w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && s.act.holds(x, ACT_F16);
+    // the k_head form, guarded here by what the node does not tell: the rows of `out` (a matcher's choice) and whether the F16 image of x fits the scratch this context holds
+    if (r.k_head && out->nb[1] % 16 == 0 && act_image_bytes(ACT_F16, K) * (size_t) N <= s.c->act_scratch_bytes) {
+        const size_t ximg = prepare_act(s, x, ACT_F16);        // (nothing to do when the image is there already)
+        x_img = true;
+        k_done = r.k_head;
+        prof_scope ps(s, "gemm_f16", 2.0 * (double) M * (double) N * (double) k_done);
+        gemm_multi_args ga;                                  // (split along K when the tiles do not fill the chip: SigLip2's fc2, 1152 x 1024 outputs, went from 79 to 24 us)
+        ga.nmat = 1; ga.m[0] = { (const uint16_t *) w->data, w->nb[1], (float *) out->data, out->nb[1], M, nullptr, 0 };
+        ga.X = (const uint16_t *) s.c->act_scratch; ga.x_rs = ximg; ga.N = N; ga.K = k_done;
+        ga.partial = gemm_split_scratch_bytes(M, N, k_done) <= s.c->gemm_partial_bytes ? (float *) gemm_partial_take(s) : nullptr; ga.partial_bytes = s.c->gemm_partial_bytes;
+        gemm_f16_multi(ga, s.st);
+        ++s.n_kernels;
+    }
+    a.W = (const char *) w->data + k_done * (w->type == GGML_TYPE_F16 ? 2 : 4); a.w_rs = w->nb[1]; a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.w_f16 = w->type == GGML_TYPE_F16;
+    if (x_img) {                                             // rows of the image: [ne13][ne12][N] x act_image_bytes
+        const size_t img = act_image_bytes(ACT_F16, K);
+        a.X = (const char *) s.c->act_scratch + k_done * 2; a.x_rs = img; a.x_nb2 = img * (size_t) N; a.x_nb3 = img * (size_t) (N * ne12); a.x_f16 = true;
+    } else {
+        a.X = (const char *) x->data + k_done * (x->type == GGML_TYPE_F16 ? 2 : 4); a.x_rs = x->nb[1]; a.x_nb2 = x->nb[2]; a.x_nb3 = x->nb[3]; a.x_f16 = x->type == GGML_TYPE_F16;
+    }
+    a.dst = (float *) out->data; a.dst_cs = out->nb[1]; a.dst_nb2 = out->nb[2]; a.dst_nb3 = out->nb[3]; a.accumulate = k_done > 0; a.bias = e.bias; a.act = e.act;
+    a.M = M; a.N = N; a.K = K - k_done; a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
+    if (s.c->gemm_partial && fa_counters(s)) { a.partial = (float *) gemm_partial_take(s); a.partial_bytes = s.c->gemm_partial_bytes; a.counters = s.c->fa_counters; a.n_counters = 1024; }
+    if (e.nsib > 0 && e.sib_taken) {
+        *e.sib_taken = false;
+        if (k_done == 0 && !x_img && w->type == GGML_TYPE_F32 && x->type == GGML_TYPE_F32) {
+            a.nmat = 1 + e.nsib;
+            for (int q = 0; q < e.nsib; ++q) { a.W_more[q] = e.sib[q].w->data; a.dst_more[q] = (float *) e.sib[q].out->data; a.bias_more[q] = e.sib[q].bias; }
+            if (gemm_any_group_ok(a)) *e.sib_taken = true; else a.nmat = 1;
+        }
+    }
+    prof_scope ps(s, w->type == GGML_TYPE_F16 ? "gemm_any_f16" : "gemm_any_f32", 2.0 * (double) M * (double) N * (double) (K - k_done) * (double) (ne12 * ne13) * (double) a.nmat);
+    gemm_any(a, s.st);
+    ++s.n_kernels;
+}
+static void mm_mmv_heads(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // attention without FLASH_ATTN_EXT: K / V^T per KV head against one activation per query head -- every head in ONE launch
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const size_t img = prepare_act(s, x, r.act);
+    mmv_args a;
+    a.W = w->data; a.w_rs = w->nb[1]; a.K = K; a.nrows = M; a.ncols = (int) N;
+    a.dst = (float *) dst->data; a.dst_cs = dst->nb[1];
+    a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
+    a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.dst_nb2 = dst->nb[2]; a.dst_nb3 = dst->nb[3];
+    if (r.act == ACT_F32) { a.act = x->data; a.act_cs = x->nb[1]; a.act_bs = x->nb[2]; }
+    else { a.act = s.c->act_scratch; a.act_cs = img; a.act_bs = (size_t) N * img; }
+    const mmv_row * row = mmv_row_for(w->type);
+    prof_scope ps(s, row->cls, (double) M * (double) row_size(w->type, K) * (double) (ne12 * ne13) / (double) (r2 * r3));
+    row->launch(a, s.st);
+    ++s.n_kernels;
+}
+static void mm_mmq(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const size_t img = prepare_act(s, x, r.act);
     const double wbytes = (double) M * (double) row_size(w->type, K);
-    // attention without FLASH_ATTN_EXT: K / V^T per KV head against one activation per query head -- every head in ONE launch
-    if ((w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32) && ne12 * ne13 > 1 && N <= MI_MMVQ_MAX_COLS && ne12 * ne13 <= 65535) {
-        mmv_args a;
-        a.W = w->data; a.w_rs = w->nb[1]; a.K = K; a.nrows = M; a.ncols = (int) N;
-        a.dst = (float *) dst->data; a.dst_cs = dst->nb[1];
-        a.nbatch = (int) (ne12 * ne13); a.ne12 = (int) ne12; a.r2 = (int) r2; a.r3 = (int) r3;
-        a.w_nb2 = w->nb[2]; a.w_nb3 = w->nb[3]; a.dst_nb2 = dst->nb[2]; a.dst_nb3 = dst->nb[3];
-        bool ok = true;
-        if (kind == ACT_F32) {
-            a.act = x->data; a.act_cs = x->nb[1]; a.act_bs = x->nb[2];
-            ok = ne13 == 1 || x->nb[3] == (size_t) ne12 * x->nb[2];
-        } else { a.act = s.c->act_scratch; a.act_cs = img; a.act_bs = (size_t) N * img; }
-        if (ok) {
-            prof_scope ps(s, mmv_class(w->type), wbytes * (double) (ne12 * ne13) / (double) (r2 * r3));
-            if (w->type == GGML_TYPE_F16) mmv_f16(a, s.st); else mmv_f32(a, s.st);
-            ++s.n_kernels;
-            return;
-        }
-    }
     for (int64_t i13 = 0; i13 < ne13; ++i13) {
         for (int64_t i12 = 0; i12 < ne12; ++i12) {
             const char * wp = (const char *) w->data + (i12 / r2) * w->nb[2] + (i13 / r3) * w->nb[3];
             char *       dp = (char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3];
-            if (mm_uses_mmq(dst)) {                                   // 9 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
-                for (int64_t c0 = 0; c0 < N; c0 += 32) {
-                    mmq_args q;
-                    q.nmat = 1; q.m[0] = { wp, w->nb[1], (float *) (dp + c0 * dst->nb[1]), dst->nb[1], M, (int) w->type };
-                    q.act = (const char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N + c0) * img; q.act_cs = img;
-                    q.K = K; q.ncols = (int) (N - c0 < 32 ? N - c0 : 32);
-                    prof_scope ps(s, w->type == GGML_TYPE_Q4_K ? "mmq_q4k" : "mmq_q6k", wbytes);
-                    mmq_kquant(q, s.st); ++s.n_kernels;
-                }
-                continue;
+            for (int64_t c0 = 0; c0 < N; c0 += 32) {
+                mmq_args q;
+                q.nmat = 1; q.m[0] = { wp, w->nb[1], (float *) (dp + c0 * dst->nb[1]), dst->nb[1], M, (int) w->type };
+                q.act = (const char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N + c0) * img; q.act_cs = img;
+                q.K = K; q.ncols = (int) (N - c0 < 32 ? N - c0 : 32);
+                prof_scope ps(s, w->type == GGML_TYPE_Q4_K ? "mmq_q4k" : "mmq_q6k", wbytes);
+                mmq_kquant(q, s.st); ++s.n_kernels;
             }
+        }
+    }
+}
+static void mm_mmv(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // the per-type mat-vec kernels, up to 8 columns per launch
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const size_t img = prepare_act(s, x, r.act);
+    const double wbytes = (double) M * (double) row_size(w->type, K);
+    for (int64_t i13 = 0; i13 < ne13; ++i13) {
+        for (int64_t i12 = 0; i12 < ne12; ++i12) {
+            const char * wp = (const char *) w->data + (i12 / r2) * w->nb[2] + (i13 / r3) * w->nb[3];
+            char *       dp = (char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3];
             const void * wv = wp; size_t wv_rs = w->nb[1]; int wv_type = w->type;
             if (is_image_quant(w->type)) {                            // mat-vec on the F16 image of the block format
                 const uint16_t * sh = weight_shadow(s, w, wp, K, M);
@@ -242,32 +228,35 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out
                 }
                 wv = sh; wv_rs = (size_t) K * 2; wv_type = GGML_TYPE_F16;
             }
+            const mmv_row * row = mmv_row_for(wv_type);
             for (int64_t c0 = 0; c0 < N; c0 += MI_MMVQ_MAX_COLS) {
                 mmv_args a;
                 a.W = wv; a.w_rs = wv_rs; a.K = K; a.nrows = M;
                 a.ncols = (int) (N - c0 < MI_MMVQ_MAX_COLS ? N - c0 : MI_MMVQ_MAX_COLS);
                 a.dst = (float *) (dp + c0 * dst->nb[1]); a.dst_cs = dst->nb[1];
-                if (kind == ACT_F32) {
+                if (r.act == ACT_F32) {
                     a.act = (const char *) x->data + i12 * x->nb[2] + i13 * x->nb[3] + c0 * x->nb[1]; a.act_cs = x->nb[1];
                 } else {
                     a.act = (const char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N + c0) * img; a.act_cs = img;
                 }
-                prof_scope ps(s, mmv_class(wv_type), wbytes);
-                switch (wv_type) {
-                    case GGML_TYPE_Q4_K: mmv_q4_K(a, s.st); break;
-                    case GGML_TYPE_Q5_K: mmv_q5_K(a, s.st); break;
-                    case GGML_TYPE_Q6_K: mmv_q6_K(a, s.st); break;
-                    case GGML_TYPE_Q8_0: mmv_q8_0(a, s.st); break;
-                    case GGML_TYPE_Q4_0: mmv_q4_0(a, s.st); break;
-                    case GGML_TYPE_Q5_0: mmv_q5_0(a, s.st); break;
-                    case GGML_TYPE_IQ4_NL: mmv_iq4_nl(a, s.st); break;
-                    case GGML_TYPE_IQ4_XS: mmv_iq4_xs(a, s.st); break;
-                    case GGML_TYPE_F16:  mmv_f16(a, s.st); break;
-                    default:             mmv_f32(a, s.st); break;
-                }
+                prof_scope ps(s, row->cls, wbytes);
+                row->launch(a, s.st);
                 ++s.n_kernels;
             }
         }
+    }
+}
+void op_mul_mat(exec_state & s, const ggml_tensor * dst) {
+    const mm_route r = route_mul_mat(dst);
+    switch (r.path) {
+        case MM_MMQ_TILE:       return mm_mmq_tile(s, dst, r);
+        case MM_GEMM_F16_HEADS: return mm_gemm_f16_heads(s, dst, r);
+        case MM_GEMM_F16:       return mm_gemm_f16(s, dst, r);
+        case MM_GEMM_BF16:      return mm_gemm_bf16(s, dst);
+        case MM_GEMM_ANY:       return mm_gemm_any(s, dst, r, mm_extras());
+        case MM_MMV_HEADS:      return mm_mmv_heads(s, dst, r);
+        case MM_MMQ:            return mm_mmq(s, dst, r);
+        case MM_MMV:            return mm_mmv(s, dst, r);
     }
 }
 
@@ -291,15 +280,20 @@ bool kq_mm_ok(const ggml_tensor * n) {
     const ggml_tensor * w = n->src[0], * x = n->src[1];
     return w->ne[2] == 1 && w->ne[3] == 1 && x->ne[2] == 1 && x->ne[3] == 1 && n->nb[0] == 4 && x->nb[0] == 4;
 }
+// would the batch-1 launch take this weight matrix?  (a probe: the activation source is checked separately)
+static bool mv1_probe(const ggml_tensor * n) {
+    const ggml_tensor * w = n->src[0];
+    mv1_args v; v.nmat = 1; v.K = w->ne[0];
+    v.m[0] = { w->data, w->nb[1], (float *) n->data, 0, nullptr, 0, w->ne[1], (int) w->type };
+    v.img = (const void *) 16;
+    return mmv1_ok(v);
+}
 // the Q8_0 twin (mmv1q.hip): MUL_MAT(Q8_0 W [K, M], f32 x [K, 1]), no broadcast -- the TTS / Token2Wav modules' decode mat-vecs
 bool q80_mv1_node(exec_state & s, const ggml_tensor * n) {
     if (!s.c->opt_mv1 || n->op != GGML_OP_MUL_MAT || is_empty(n)) return false;
     const ggml_tensor * w = n->src[0], * x = n->src[1];
     if ((w->type != GGML_TYPE_Q8_0 && w->type != GGML_TYPE_F16) || x->type != GGML_TYPE_F32 || w->ne[2] != 1 || w->ne[3] != 1 || x->ne[1] != 1 || x->ne[2] != 1 || x->ne[3] != 1 || n->nb[0] != 4 || x->nb[0] != 4) return false;
-    mv1_args v; v.nmat = 1; v.K = w->ne[0];
-    v.m[0] = { w->data, w->nb[1], (float *) n->data, 0, nullptr, 0, w->ne[1], (int) w->type };
-    v.img = (const void *) 16;
-    return mmv1_ok(v);
+    return mv1_probe(n);
 }
 // batch-1 decode form (mmv1.hip): one column, Q4_K / Q6_K, K a multiple of 256 up to 16384, aligned rows; or the Q8_0 twin
 bool mv1_node_ok(exec_state & s, const ggml_tensor * n) {
@@ -307,10 +301,7 @@ bool mv1_node_ok(exec_state & s, const ggml_tensor * n) {
     if (!s.c->opt_mv1 || !plain_kq_matvec(n, 1)) return false;
     const ggml_tensor * w = n->src[0], * x = n->src[1];
     if (x->ne[1] != 1 || x->type != GGML_TYPE_F32 || (w->type != GGML_TYPE_Q4_K && w->type != GGML_TYPE_Q6_K)) return false;
-    mv1_args v; v.nmat = 1; v.K = w->ne[0];
-    v.m[0] = { w->data, w->nb[1], (float *) n->data, 0, nullptr, 0, w->ne[1], (int) w->type };
-    v.img = (const void *) 16;                                             // (source checked separately)
-    return mmv1_ok(v);
+    return mv1_probe(n);
 }
 // activation source of an mmv1 launch on x: the pending norm (computed inside the launch), the cached Q8_K image, the f32 row itself
 // (quantised inside the launch), or -- when an output would overwrite x while the launch reads it -- a quantise launch first

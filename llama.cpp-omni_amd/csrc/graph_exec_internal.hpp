@@ -10,9 +10,11 @@
 namespace mi {
 
 // ------------------------------------------------------------------------------------------------ MUL_MAT
-// out / bias: the ADD of a [M] row vector behind the mat-mul, folded into the any-shape GEMM's epilogue (exec_mul_mat decides; only that path takes them)
+// What a matcher may fold into the any-shape GEMM's launch (exec_mul_mat decides; no other path takes them, so mm_gemm_any is called directly):
+// out / bias: the ADD of a [M] row vector behind the mat-mul, in the epilogue (`out` = that ADD, or the GELU behind it with act = 1; null: the node itself)
 // sib / nsib: up to two more F32-weight mat-muls over the same activation (same weight shape and strides) for the launch; *sib_taken tells whether they went along
 struct mm_sibling { const ggml_tensor * w; const ggml_tensor * out; const float * bias; };
+struct mm_extras { const ggml_tensor * out = nullptr; const float * bias = nullptr; const mm_sibling * sib = nullptr; int nsib = 0; bool * sib_taken = nullptr; int act = 0; };
 
 // RMS_NORM(j) -> MUL(w[D]) -> ROPE [-> SET_ROWS of the rotated rows viewed as [D*H, T] into an f16 table]; shape checks only
 struct nr_chain {
@@ -53,9 +55,9 @@ void lazy_net(exec_state & s, int i);
 void lazy_materialise(exec_state & s, const ggml_tensor * t, int reader_op = -1);
 byte_range range_of(const tdesc & d);
 size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind);
-const char * mmv_class(int type);
 const uint16_t * weight_shadow(exec_state & s, const ggml_tensor * w, const char * wp, int64_t K, int64_t M);
-void op_mul_mat(exec_state & s, const ggml_tensor * dst, const ggml_tensor * out = nullptr, const float * bias = nullptr, const mm_sibling * sib = nullptr, int nsib = 0, bool * sib_taken = nullptr, int act = 0);
+void op_mul_mat(exec_state & s, const ggml_tensor * dst);                                             // switch over route_mul_mat(dst).path
+void mm_gemm_any(exec_state & s, const ggml_tensor * dst, const mm_route & r, const mm_extras & e);      // the MM_GEMM_ANY path, r = route_mul_mat(dst) (any other route: an abort)
 bool plain_kq_matvec(const ggml_tensor * n, int max_cols);
 bool kq_mm_ok(const ggml_tensor * n);
 bool q80_mv1_node(exec_state & s, const ggml_tensor * n);

@@ -313,7 +313,8 @@ void exec_mul_mat(exec_state & s, int i) {
     ggml_tensor * n = g->nodes[i];
     if (s.c->opt_fusion && exec_gemm_group(s, i)) return;
     const bool q80 = s.c->opt_fusion && q80_mv1_node(s, n);                  // Q8_0, one column: the same fusions on mmv1q.hip
-    if (s.c->opt_fusion && mm_takes_gemm_any(n) && !is_out(s, n)) {
+    const mm_route rt = route_mul_mat(n);
+    if (s.c->opt_fusion && rt.path == MM_GEMM_ANY && !is_out(s, n)) {
         // the bias ADD behind an F32-weight / odd-K linear layer (Token2Wav's DiT and HiFT blocks): a [M] row vector, the only reader, the next launch -> the GEMM's epilogue
         static const bool off = getenv("MI355X_NO_GEMM_ANY_BIAS") != nullptr;
         const int ai = off ? -1 : sole_user(s, n);
@@ -365,13 +366,13 @@ void exec_mul_mat(exec_state & s, int i) {
                     for (int d = 0; oku && d < 4; ++d) oku = U->ne[d] == A->ne[d] && U->nb[d] == A->nb[d];
                     oku = oku && !overlap(range_of(U), range_of(n->src[0])) && !overlap(range_of(U), range_of(n->src[1])) && !overlap(range_of(U), range_of(r));
                     if (oku) {
-                        op_mul_mat(s, n, U, (const float *) r->data, nullptr, 0, nullptr, 1);
+                        { mm_extras e; e.out = U; e.bias = (const float *) r->data; e.act = 1; mm_gemm_any(s, n, rt, e); }
                         s.done[ai] = 1; s.done[ui] = 1; s.n_fused += 2;
                         note_write(s, U);
                         return;
                     }
                 }
-                op_mul_mat(s, n, A, (const float *) r->data, sib, nsib, &taken);
+                { mm_extras e; e.out = A; e.bias = (const float *) r->data; e.sib = sib; e.nsib = nsib; e.sib_taken = &taken; mm_gemm_any(s, n, rt, e); }
                 s.done[ai] = 1; ++s.n_fused;
                 note_write(s, A);
                 if (taken) for (int q = 0; q < nsib; ++q) { s.done[sib_mm[q]] = 1; s.done[sib_add[q]] = 1; s.n_fused += 2; note_write(s, sib[q].out); }

@@ -38,21 +38,6 @@ enum act_kind { ACT_NONE = 0, ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32, ACT_Q8KT, ACT_
 static inline bool is_image_quant(int t) {
     return t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K;
 }
-// Q4_0 / Q5_0: integer mat-vec kernels on Q8_0 activations up to 8 columns (mmvq.hip), the F16 image from 9 columns on
-static inline bool is_q40_like(int t) { return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q5_0; }
-// IQ4_NL / IQ4_XS: integer mat-vec kernels up to 8 columns (mmvq.hip: IQ4_NL on Q8_0 images, IQ4_XS on Q8_K images), the F16 image from 9 columns on.
-// IQ4_XS shares the Q8_K image with the K-quants, but none of the K-quant launch forms (fusions, mmq, the k_mv2 engine) takes it: those test is_kquant / the type.
-static inline bool is_iq4(int t) { return t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_IQ4_XS; }
-static inline act_kind act_kind_for(int wtype) {
-    if (is_image_quant(wtype)) return ACT_F16;
-    switch (wtype) {
-        case GGML_TYPE_Q4_K: case GGML_TYPE_Q5_K: case GGML_TYPE_Q6_K: case GGML_TYPE_IQ4_XS: return ACT_Q8K;
-        case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_0: case GGML_TYPE_Q5_0: case GGML_TYPE_IQ4_NL: return ACT_Q80;
-        case GGML_TYPE_F16:  return ACT_F16;
-        case GGML_TYPE_F32:  return ACT_F32;
-        default: return ACT_NONE;
-    }
-}
 static inline size_t act_image_bytes(act_kind k, int64_t K) {
     switch (k) {
         case ACT_Q8K: return q8k_image_bytes(K);
@@ -189,14 +174,29 @@ static inline void prof_drain(backend_ctx * c) {
 // ---- graph_plan.cpp
 static const int64_t ROPE_TABLE_MIN_TOKENS = 32;
 static const int64_t GEMM_MIN_COLS = MI_MMVQ_MAX_COLS + 1;
-bool mm_uses_mmq(const ggml_tensor * n);
+// Which kernel family a MUL_MAT node takes: decided once, by route_mul_mat, for the planner (supports_op), the scratch sizing and the executor (op_mul_mat).
+enum mm_path { MM_MMQ_TILE, MM_GEMM_F16_HEADS, MM_GEMM_F16, MM_GEMM_BF16, MM_GEMM_ANY, MM_MMV_HEADS, MM_MMQ, MM_MMV };
+struct mm_route {
+    mm_path  path;
+    act_kind act;            // the image of x the path reads (prepare_act; ACT_F32 / ACT_NONE: the f32 rows themselves)
+    bool     gemm;           // the F16 GEMM's conditions hold (mm_uses_gemm): MM_GEMM_F16*, and MM_MMQ_TILE as its sub-case -- unless MI355X_NO_GEMM / _MMQ_MAX_COLS under 8 leave the tile kernel alone
+    bool     w_image;        // the weights are read through their F16 image (shadow, else w_scratch) rather than as blocks
+    int64_t  k_head;         // MM_GEMM_ANY: the K - K % 64 columns the F16 GEMM may take first (0: none)
+    int64_t  k_head_sized;   // what graph_gemm_partial_need reserves split-K scratch for: k_head's shape rule alone, on any path behind the F16 GEMM's
+};
+mm_route route_mul_mat(const ggml_tensor * n);
+// one row per admitted weight type (null: none; BF16 has a path of its own): the image its mat-vec kernels read, their launcher (up to 8 columns) and profile class
+struct mmv_row { int type; act_kind act; void (*launch)(const mmv_args &, hipStream_t); const char * cls; };
+const mmv_row * mmv_row_for(int wtype);
+bool mm_uses_mmq(const ggml_tensor * n);                // the views of the route the fusion matchers ask for
 bool mm_uses_gemm(const ggml_tensor * n);
 bool mm_uses_mmq_tile(const ggml_tensor * n);
+bool mm_takes_gemm_any(const ggml_tensor * n);
+bool mm_uses_gemm_any_f16(const ggml_tensor * n);
 act_kind gemm_act_kind(const ggml_tensor * n);          // ACT_F16, or ACT_F16Q for K-quant weights (option "prefill_q8k")
 void prefill_q8k_set_mode(int m);
 void mmq_tile_set_mode(int m);
 int64_t mmq_max_cols();
-bool mm_uses_gemm_any_f16(const ggml_tensor * n);
 size_t graph_act_scratch_need(const ggml_cgraph * g);
 size_t graph_w_scratch_need(const ggml_cgraph * g);
 void fill_fattn_args(const ggml_tensor * n, fattn_args & f, tdesc & m);
@@ -206,7 +206,6 @@ int64_t gemm_group_split_max_cols();
 size_t graph_gemm_partial_need(const ggml_cgraph * g);
 bool ensure_scratch(backend_ctx * c, void ** p, size_t * have, size_t need);
 // ---- graph_exec.cpp
-bool mm_takes_gemm_any(const ggml_tensor * n);
 long attn_vrows_launches();                           // flash-attention-off chains run on V rows that exec_gemm_group wrote (graph_exec_llm.cpp)
 void run_nodes(exec_state & s, ggml_cgraph * g);
 } // namespace mi

@@ -17,7 +17,7 @@ bool supports_op(const ggml_tensor * op) {
             if (s0->type == GGML_TYPE_BF16)                          // BF16 weights: the any-shape f32-MFMA GEMM at every column count (gemm_any.hip)
                 return s1->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && s0->nb[0] == 2 && s1->nb[0] == 4 && op->nb[0] == 4 && s0->nb[1] >= (size_t) s0->ne[0] * 2 &&
                        s0->ne[2] != 0 && s0->ne[3] != 0 && s1->ne[2] % s0->ne[2] == 0 && s1->ne[3] % s0->ne[3] == 0 && s1->ne[2] * s1->ne[3] <= 65535;
-            const act_kind k = act_kind_for(s0->type);
+            const act_kind k = mmv_row_for(s0->type) ? mmv_row_for(s0->type)->act : ACT_NONE;
             if (k == ACT_NONE || op->type != GGML_TYPE_F32) return false;
             if (s1->type != GGML_TYPE_F32 && !(s1->type == GGML_TYPE_F16 && k == ACT_F16)) return false;      // F16 x F16: the convolutions' mat-mul
             if (s0->ne[0] % blck_size(s0->type) != 0) return false;
@@ -30,8 +30,9 @@ bool supports_op(const ggml_tensor * op) {
             }
             // every mat-vec path (up to 8 columns per launch; F32 weights at any width) stages one activation column in LDS: a column
             // beyond 152 KiB has no kernel (e.g. attention without FLASH_ATTN_EXT past ~77k cache rows: K = n_kv) -> leave it to the CPU
-            if (!mm_uses_gemm(op) && !mm_uses_mmq(op) && !mm_takes_gemm_any(op)) {       // (gemm_any stages nothing in LDS)
-                const size_t col = k == ACT_F32 ? (size_t) s0->ne[0] * 4 : act_image_bytes(is_image_quant(s0->type) ? ACT_F16 : k, s0->ne[0]);
+            const mm_route r = route_mul_mat(op);
+            if (!r.gemm && r.path != MM_MMQ && r.path != MM_GEMM_ANY) {                  // (gemm_any stages nothing in LDS)
+                const size_t col = k == ACT_F32 ? (size_t) s0->ne[0] * 4 : act_image_bytes(k, s0->ne[0]);
                 if (col > (size_t) 152 * 1024) return false;
             }
             return true;
@@ -156,7 +157,27 @@ bool supports_op(const ggml_tensor * op) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------ scratch sizing
+// ------------------------------------------------------------------------------------------------ MUL_MAT routing
+static const mmv_row MMV_ROWS[] = {
+    { GGML_TYPE_Q4_K,   ACT_Q8K, mmv_q4_K,   "mmv_q4k"   },
+    { GGML_TYPE_Q5_K,   ACT_Q8K, mmv_q5_K,   "mmv_f32"   },      // (Q5_K, Q4_0 and Q5_0 launches have always been booked under mmv_f32)
+    { GGML_TYPE_Q6_K,   ACT_Q8K, mmv_q6_K,   "mmv_q6k"   },
+    { GGML_TYPE_Q8_0,   ACT_Q80, mmv_q8_0,   "mmv_q80"   },
+    // Q4_0 / Q5_0: integer mat-vec kernels on Q8_0 activations up to 8 columns (mmvq.hip), the F16 image from 9 columns on
+    { GGML_TYPE_Q4_0,   ACT_Q80, mmv_q4_0,   "mmv_f32"   },
+    { GGML_TYPE_Q5_0,   ACT_Q80, mmv_q5_0,   "mmv_f32"   },
+    // IQ4_NL / IQ4_XS: integer mat-vec kernels up to 8 columns (mmvq.hip: IQ4_NL on Q8_0 images, IQ4_XS on Q8_K images), the F16 image from 9 columns on.
+    // IQ4_XS shares the Q8_K image with the K-quants, but none of the K-quant launch forms (fusions, mmq, the k_mv2 engine) takes it: those test is_kquant / the type.
+    { GGML_TYPE_IQ4_NL, ACT_Q80, mmv_iq4_nl, "mmv_iq4nl" },
+    { GGML_TYPE_IQ4_XS, ACT_Q8K, mmv_iq4_xs, "mmv_iq4xs" },
+    { GGML_TYPE_F16,    ACT_F16, mmv_f16,    "mmv_f16"   },
+    { GGML_TYPE_F32,    ACT_F32, mmv_f32,    "mmv_f32"   },
+};
+const mmv_row * mmv_row_for(int wtype) {
+    if (is_image_quant(wtype)) wtype = GGML_TYPE_F16;      // no integer-dot kernels: everything runs on the F16 image, the mat-vec with the F16 row's launcher
+    for (const mmv_row & r : MMV_ROWS) if (r.type == wtype) return &r;
+    return nullptr;
+}
 // batches of more than 8 columns go to the MFMA GEMM (activations rounded to f16; quantised weights de-quantised to f16 first)
 // ... except K-quant weights against up to MMQ_MAX_COLS columns (several sequences decoded together, drafts, small ubatches): those
 // read the quantised blocks themselves on the int8 matrix cores (mmq.hip) -- 0.56 / 0.82 bytes per weight instead of the 2 of an f16 image
@@ -169,21 +190,21 @@ static int64_t mmq_min_cols() {       // narrower batches stay on the dot4 mat-v
     static const int64_t v = getenv("MI355X_MMQ_MIN_COLS") ? atoll(getenv("MI355X_MMQ_MIN_COLS")) : 6;
     return v;
 }
-bool mm_uses_mmq(const ggml_tensor * n) {
+static bool mmq_takes(const ggml_tensor * n) {
     const ggml_tensor * w = n->src[0], * x = n->src[1];
     return (w->type == GGML_TYPE_Q4_K || w->type == GGML_TYPE_Q5_K || w->type == GGML_TYPE_Q6_K) && x->type == GGML_TYPE_F32 && x->ne[1] >= mmq_min_cols() && x->ne[1] <= mmq_max_cols() &&
            mmq_ok(w->type, w->ne[0], w->data, w->nb[1]) && (w->ne[2] == 1 || mmq_ok(w->type, w->ne[0], (const char *) w->data + w->nb[2], w->nb[1])) &&
            (w->ne[3] == 1 || mmq_ok(w->type, w->ne[0], (const char *) w->data + w->nb[3], w->nb[1]));
 }
 // Q4_K weights against a prefill ubatch (more than mmq_max_cols() columns): the tiled int8-MFMA kernel on the blocks themselves and the Q8_K-quantised
-// activations -- the oracle's integers (mmq_tile.hip).  A sub-case of mm_uses_gemm(): the grouping / residual / split-K machinery of the GEMM path serves it.
+// activations -- the oracle's integers (mmq_tile.hip).  A sub-case of the F16 GEMM (mm_uses_gemm): the grouping / residual / split-K machinery of the GEMM path serves it.
 static int g_mmq_tile = -1;                                   // option "mmq_tile": -1 = MI355X_MMQ_TILE decides (default off), 0 off, 1 on
 void mmq_tile_set_mode(int m) { g_mmq_tile = m; }
-bool mm_uses_mmq_tile(const ggml_tensor * n) {
+static bool mmq_tile_takes(const ggml_tensor * n) {
     static const int env = getenv("MI355X_MMQ_TILE") ? atoi(getenv("MI355X_MMQ_TILE")) : 0;      // (off by default: exact, but slower than the F16-image GEMM -- DESIGN.md section 7, profiles/r05_mmq_tile.txt)
     if (!(g_mmq_tile >= 0 ? g_mmq_tile : env)) return false;
     const ggml_tensor * w = n->src[0], * x = n->src[1];
-    if (n->op != GGML_OP_MUL_MAT || !w || !x || w->type != GGML_TYPE_Q4_K || x->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32) return false;
+    if (w->type != GGML_TYPE_Q4_K || x->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32) return false;
     if (x->ne[1] <= mmq_max_cols() || x->ne[2] != 1 || x->ne[3] != 1 || w->ne[2] != 1 || w->ne[3] != 1 || x->nb[0] != 4 || n->nb[0] != 4) return false;
     if (x->nb[1] % 16 != 0 || ((uintptr_t) x->data & 15) != 0) return false;
     return mmq_tile_ok(w->type, w->ne[0], w->data, w->nb[1]);
@@ -202,12 +223,12 @@ act_kind gemm_act_kind(const ggml_tensor * n) {
     const bool kq = t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K;
     return kq && x->type == GGML_TYPE_F32 && x->ne[0] % 256 == 0 ? ACT_F16Q : ACT_F16;
 }
-bool mm_uses_gemm(const ggml_tensor * n) {
+static bool gemm_f16_takes(const ggml_tensor * n) {
     const ggml_tensor * w = n->src[0], * x = n->src[1];
     static const bool no_gemm = getenv("MI355X_NO_GEMM") != nullptr;
     if (x->ne[1] < GEMM_MIN_COLS || no_gemm) return false;
-    if (mm_uses_mmq(n)) return false;
-    if (w->type != GGML_TYPE_F16 && w->type != GGML_TYPE_Q4_K && w->type != GGML_TYPE_Q5_K && w->type != GGML_TYPE_Q6_K && w->type != GGML_TYPE_Q8_0 && !is_image_quant(w->type) && !is_q40_like(w->type) && !is_iq4(w->type)) return false;
+    if (mmq_takes(n)) return false;
+    if (!mmv_row_for(w->type) || w->type == GGML_TYPE_F32) return false;         // F16 and every block format, through its F16 image
     const int64_t K = w->ne[0];
     if (K % 32 != 0) return false;
     if (w->type == GGML_TYPE_F16 && (w->nb[1] % 16 != 0 || w->nb[2] % 16 != 0 || w->nb[3] % 16 != 0 || ((uintptr_t) w->data & 15) != 0)) return false;
@@ -216,22 +237,61 @@ bool mm_uses_gemm(const ggml_tensor * n) {
     if (w->type == GGML_TYPE_F16 && x->ne[2] * x->ne[3] > 1 && K % 64 != 0 && x->type == GGML_TYPE_F32 && x->ne[2] * x->ne[3] <= 65535) return false;
     return true;
 }
-// MUL_MAT that op_mul_mat sends to the any-shape GEMM's f16 kernel (gemm_any.hip k_gemm_any_h): F16 weights the DMA GEMMs do not take (odd K,
-// unaligned rows) against more than 8 f32 columns -- it reads a ready-made f16 activation image as well as the f32 rows
-bool mm_uses_gemm_any_f16(const ggml_tensor * n) {
+// The one place where shape, type, stride and alignment choose the path of a MUL_MAT node that supports_op admits; the order is op_mul_mat's.
+mm_route route_mul_mat(const ggml_tensor * n) {
     const ggml_tensor * w = n->src[0], * x = n->src[1];
-    static const bool off = getenv("MI355X_NO_GEMM_ANY") != nullptr || getenv("MI355X_NO_GEMM_ANY_H") != nullptr;
-    return !off && !mm_uses_gemm(n) && w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && x->ne[1] > MI_MMVQ_MAX_COLS && x->nb[0] == 4 && w->nb[0] == 2 && n->nb[0] == 4 &&
-           x->ne[2] * x->ne[3] <= 65535 && w->ne[1] < (1ll << 31) && x->ne[1] < (1ll << 31) && w->ne[0] < (1ll << 31);
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], nbatch = x->ne[2] * x->ne[3];
+    const mmv_row * row = mmv_row_for(w->type);
+    mm_route r = { MM_MMV, row ? row->act : ACT_NONE, gemm_f16_takes(n), false, 0, 0 };
+    if (mmq_tile_takes(n)) { r.path = MM_MMQ_TILE; r.act = ACT_Q8KT; return r; }      // Q4_K x a prefill ubatch: the tiled int8-MFMA kernel on the Q8_K image (mmq_tile.hip)
+    if (r.gemm) {
+        // ---- prefill: MFMA GEMM.  X -> f16 rows (what the reference does for F16 weights, ggml-cpu.c:1245-1268); quantised W -> f16
+        r.act = nbatch == 1 ? gemm_act_kind(n) : ACT_F16;
+        // attention without FLASH_ATTN_EXT at prefill: every head's K.Q^T (or V^T.P) product in one launch  (F16 rows here are 16-byte aligned: gemm_f16_takes)
+        if (w->type == GGML_TYPE_F16 && nbatch > 1 && nbatch <= 65535 && K % 64 == 0 && n->nb[0] == 4) { r.path = MM_GEMM_F16_HEADS; return r; }
+        r.path = MM_GEMM_F16; r.w_image = w->type != GGML_TYPE_F16;
+        return r;
+    }
+    if (w->type == GGML_TYPE_BF16) { r.path = MM_GEMM_BF16; return r; }               // the any-shape f32-MFMA GEMM at every column count (gemm_any.hip)
+    // F16 weights, K a few columns past a multiple of 64 (SigLip2's n_ff 4304): the F16 MFMA GEMM takes the first K - K % 64 columns, the any-shape kernel adds the tail
+    if (w->type == GGML_TYPE_F16 && x->type == GGML_TYPE_F32 && nbatch == 1 && K % 64 != 0 && K >= 512 && N > MI_MMVQ_MAX_COLS) r.k_head_sized = K - K % 64;
+    // more than 8 columns against F32 weights, or F16 weights with a contraction length the F16 GEMM does not take (the omni encoders, Token2Wav):
+    // one f32-MFMA launch over every (head, batch) instead of a mat-vec launch per 8 columns per head
+    static const bool no_gemm_any = getenv("MI355X_NO_GEMM_ANY") != nullptr;
+    if (!no_gemm_any && (w->type == GGML_TYPE_F32 || w->type == GGML_TYPE_F16) && N > MI_MMVQ_MAX_COLS &&
+        ((x->type == GGML_TYPE_F32 && x->nb[0] == 4) || (x->type == GGML_TYPE_F16 && x->nb[0] == 2 && w->type == GGML_TYPE_F16)) && w->nb[0] == (w->type == GGML_TYPE_F16 ? 2u : 4u) && n->nb[0] == 4 &&
+        nbatch <= 65535 && M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31)) {
+        r.path = MM_GEMM_ANY;
+        if (w->nb[1] % 16 == 0 && ((uintptr_t) w->data & 15) == 0) r.k_head = r.k_head_sized;
+        return r;
+    }
+    // attention without FLASH_ATTN_EXT: K / V^T per KV head against one activation per query head -- every head in ONE launch  (f32 rows are read in place: one batch stride)
+    if ((w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32) && nbatch > 1 && N <= MI_MMVQ_MAX_COLS && nbatch <= 65535 &&
+        (r.act != ACT_F32 || x->ne[3] == 1 || x->nb[3] == (size_t) x->ne[2] * x->nb[2])) { r.path = MM_MMV_HEADS; return r; }
+    if (mmq_takes(n)) { r.path = MM_MMQ; return r; }                                  // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
+    r.w_image = is_image_quant(w->type);                                              // mat-vec on the F16 image of the block format
+    return r;
 }
+bool mm_uses_mmq(const ggml_tensor * n)       { return route_mul_mat(n).path == MM_MMQ; }
+bool mm_uses_mmq_tile(const ggml_tensor * n)  { return route_mul_mat(n).path == MM_MMQ_TILE; }
+bool mm_takes_gemm_any(const ggml_tensor * n) { return route_mul_mat(n).path == MM_GEMM_ANY; }
+bool mm_uses_gemm(const ggml_tensor * n)      { return route_mul_mat(n).gemm; }
+// MM_GEMM_ANY on the f16 kernel (gemm_any.hip k_gemm_any_h): F16 weights the DMA GEMMs do not take (odd K, unaligned rows) against more than 8 f32 columns -- it reads
+// a ready-made f16 activation image as well as the f32 rows.  MI355X_NO_GEMM_ANY_H: the node stays on its path, but no producer emits the image for it.
+bool mm_uses_gemm_any_f16(const ggml_tensor * n) {
+    static const bool off = getenv("MI355X_NO_GEMM_ANY_H") != nullptr;
+    return !off && n->src[0]->type == GGML_TYPE_F16 && n->src[1]->type == GGML_TYPE_F32 && route_mul_mat(n).path == MM_GEMM_ANY;
+}
+
+// ------------------------------------------------------------------------------------------------ scratch sizing
 size_t graph_act_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
         if (n->op != GGML_OP_MUL_MAT || is_empty(n)) continue;
-        const act_kind k = mm_uses_gemm(n) ? ACT_F16 : act_kind_for(n->src[0]->type);
-        size_t b = act_image_bytes(k, n->src[1]->ne[0]) * (size_t) (n->src[1]->ne[1] * n->src[1]->ne[2] * n->src[1]->ne[3]);
-        if (mm_uses_mmq_tile(n)) b = mmqt_image_bytes(n->src[1]->ne[0], n->src[1]->ne[1]);
+        const mm_route r = route_mul_mat(n);
+        const size_t b = r.path == MM_MMQ_TILE ? mmqt_image_bytes(n->src[1]->ne[0], n->src[1]->ne[1])
+                                               : act_image_bytes(r.act, n->src[1]->ne[0]) * (size_t) (n->src[1]->ne[1] * n->src[1]->ne[2] * n->src[1]->ne[3]);
         if (b > need) need = b;
     }
     return need;
@@ -240,7 +300,7 @@ size_t graph_w_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
-        if (n->op != GGML_OP_MUL_MAT || is_empty(n) || n->src[0]->type == GGML_TYPE_F16 || !(mm_uses_gemm(n) || is_image_quant(n->src[0]->type)) || mm_uses_mmq_tile(n)) continue;
+        if (n->op != GGML_OP_MUL_MAT || is_empty(n) || !route_mul_mat(n).w_image) continue;
         const size_t b = (size_t) n->src[0]->ne[0] * (size_t) n->src[0]->ne[1] * 2;
         if (b > need) need = b;
     }
@@ -295,7 +355,8 @@ size_t graph_gemm_partial_need(const ggml_cgraph * g) {
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
         if (n->op != GGML_OP_MUL_MAT || is_empty(n)) continue;
-        if (mm_takes_gemm_any(n) && n->src[0]->type == GGML_TYPE_F32 && n->src[1]->type == GGML_TYPE_F32) {      // small f32 x f32 products may split K over workgroups (gemm_any.hip)
+        const mm_route r = route_mul_mat(n);
+        if (r.path == MM_GEMM_ANY && n->src[0]->type == GGML_TYPE_F32 && n->src[1]->type == GGML_TYPE_F32) {      // small f32 x f32 products may split K over workgroups (gemm_any.hip)
             const int nbatch = (int) (n->src[1]->ne[2] * n->src[1]->ne[3]);
             size_t b = gemm_any_split_scratch_bytes(n->src[0]->ne[1], n->src[1]->ne[1], n->src[0]->ne[0], nbatch, true);
             if (n->src[0]->op == GGML_OP_RESHAPE && n->src[0]->src[0] && n->src[0]->src[0]->op == GGML_OP_IM2COL) {      // a streaming causal convolution's per-batch-element product: run with the roles swapped, both batch elements in one launch (exec_causal_conv)
@@ -305,12 +366,9 @@ size_t graph_gemm_partial_need(const ggml_cgraph * g) {
             if (b > need) need = b;
         }
         if (n->src[1]->ne[2] != 1 || n->src[1]->ne[3] != 1) continue;
-        if (!mm_uses_gemm(n)) {                              // the split form of op_mul_mat (F16 weights, K a few columns past a multiple of 64): its MFMA part is a lone, usually under-filled GEMM
-            const int64_t K = n->src[0]->ne[0];
-            if (n->src[0]->type == GGML_TYPE_F16 && n->src[1]->type == GGML_TYPE_F32 && K % 64 != 0 && K >= 512 && n->src[1]->ne[1] > MI_MMVQ_MAX_COLS) {
-                const size_t b = gemm_split_scratch_bytes(n->src[0]->ne[1], n->src[1]->ne[1], K - K % 64);
-                if (b > need) need = b;
-            }
+        if (!r.gemm) {                                       // the k_head form of the any-shape GEMM: its MFMA part is a lone, usually under-filled GEMM
+            const size_t b = r.k_head_sized ? gemm_split_scratch_bytes(n->src[0]->ne[1], n->src[1]->ne[1], r.k_head_sized) : 0;
+            if (b > need) need = b;
             continue;
         }
         int64_t m_sum = n->src[0]->ne[1];                    // the mat-muls that share this activation may go out as one launch (exec_gemm_group)
@@ -322,7 +380,7 @@ size_t graph_gemm_partial_need(const ggml_cgraph * g) {
             }
         }
         size_t b = gemm_split_scratch_bytes(m_sum, n->src[1]->ne[1], n->src[0]->ne[0]);
-        if (mm_uses_mmq_tile(n)) {                           // (its own split rule: one workgroup per CU)
+        if (r.path == MM_MMQ_TILE) {                         // (its own split rule: one workgroup per CU)
             const size_t b1 = mmq_tile_split_scratch_bytes(n->src[0]->ne[1], n->src[1]->ne[1], n->src[0]->ne[0]), b2 = mmq_tile_split_scratch_bytes(m_sum, n->src[1]->ne[1], n->src[0]->ne[0]);
             if (b1 > b) b = b1;
             if (b2 > b) b = b2;
@@ -350,6 +408,5 @@ bool ensure_scratch(backend_ctx * c, void ** p, size_t * have, size_t need) {
     drop_graph_execs(c);                                    // captured graphs baked the old pointer in
     return true;
 }
-
 
 } // namespace mi
