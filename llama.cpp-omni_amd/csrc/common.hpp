@@ -199,3 +199,10 @@ MI_HD static inline size_t q80_image_bytes(int64_t K) {
     size_t n = (size_t) K + (size_t) K / 32 * 4;
     return (n + 15) & ~(size_t) 15;
 }
+// Q8_1 image (activations for Q4_1 / Q5_1 weights; reference x86 path arch/x86/quants.c quantize_row_q8_1): the Q8_0 image's qs and d, plus
+// s = f16(d_f32 * sum of the block's qs), the factor of the weights' per-block minimum:
+//   [ qs : K int8 ][ d : K/32 float (f16-rounded value) ][ s : K/32 float (f16-rounded value) ][ pad ]
+MI_HD static inline size_t q81_image_bytes(int64_t K) {
+    size_t n = (size_t) K + (size_t) K / 32 * 8;
+    return (n + 15) & ~(size_t) 15;
+}

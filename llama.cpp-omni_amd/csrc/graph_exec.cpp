@@ -19,6 +19,7 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
         else if (kind == ACT_Q8KT) quantize_q8k_tile_image(src, xs, out, K, rows, s.st);
         else if (kind == ACT_F16Q) convert_f32_f16q_rows(src, xs, (uint16_t *) out, img, K, rows, s.st);
         else if (kind == ACT_Q80) quantize_q80_image(src, xs, out, K, rows, s.st);
+        else if (kind == ACT_Q81) quantize_q81_image(src, xs, out, K, rows, s.st);
         else                      convert_f32_f16_rows(src, xs, (uint16_t *) out, img, K, rows, s.st);
         ++s.n_kernels;
     };
@@ -218,20 +219,10 @@ static void mm_mmv(exec_state & s, const ggml_tensor * dst, const mm_route & r) 
         for (int64_t i12 = 0; i12 < ne12; ++i12) {
             const char * wp = (const char *) w->data + (i12 / r2) * w->nb[2] + (i13 / r3) * w->nb[3];
             char *       dp = (char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3];
-            const void * wv = wp; size_t wv_rs = w->nb[1]; int wv_type = w->type;
-            if (is_image_quant(w->type)) {                            // mat-vec on the F16 image of the block format
-                const uint16_t * sh = weight_shadow(s, w, wp, K, M);
-                if (!sh) {
-                    prof_scope ps(s, "dequant_f16", wbytes);
-                    dequant_rows_f16(w->type, wp, w->nb[1], (uint16_t *) s.c->w_scratch, (size_t) K * 2, K, M, s.st); ++s.n_kernels;
-                    sh = (const uint16_t *) s.c->w_scratch;
-                }
-                wv = sh; wv_rs = (size_t) K * 2; wv_type = GGML_TYPE_F16;
-            }
-            const mmv_row * row = mmv_row_for(wv_type);
+            const mmv_row * row = mmv_row_for(w->type);               // every admitted type reads its own blocks: no weight image is built here
             for (int64_t c0 = 0; c0 < N; c0 += MI_MMVQ_MAX_COLS) {
                 mmv_args a;
-                a.W = wv; a.w_rs = wv_rs; a.K = K; a.nrows = M;
+                a.W = wp; a.w_rs = w->nb[1]; a.K = K; a.nrows = M;
                 a.ncols = (int) (N - c0 < MI_MMVQ_MAX_COLS ? N - c0 : MI_MMVQ_MAX_COLS);
                 a.dst = (float *) (dp + c0 * dst->nb[1]); a.dst_cs = dst->nb[1];
                 if (r.act == ACT_F32) {

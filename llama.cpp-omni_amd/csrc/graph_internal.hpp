@@ -32,9 +32,11 @@ struct byte_range { const char * lo; const char * hi; };
 static inline byte_range range_of(const ggml_tensor * t) { const char * p = (const char *) t->data; return { p, p + nbytes(t) }; }
 static inline bool overlap(byte_range a, byte_range b) { return a.lo < b.hi && b.lo < a.hi && a.lo != a.hi && b.lo != b.hi; }
 
-enum act_kind { ACT_NONE = 0, ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32, ACT_Q8KT, ACT_F16Q };      // F16Q: f16 rows of the Q8_K-quantised values (what the F16-image GEMMs of K-quant weights multiply with)      // Q8KT: the block-major Q8_K image of a whole ubatch (mmq_tile.hip), not a per-row format
-// block formats without integer-dot kernels of their own: every MUL_MAT runs on the F16 image of the weights (resident for model
-// tensors, shadow.hpp; else de-quantised into scratch per call) with f16-rounded activations -- the arithmetic of the prefill GEMM
+enum act_kind { ACT_NONE = 0, ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32, ACT_Q8KT, ACT_F16Q, ACT_Q81 };      // Q81: the Q8_0 image plus the per-block s = d * sum(qs) (Q4_1 / Q5_1 weights)      // F16Q: f16 rows of the Q8_K-quantised values (what the F16-image GEMMs of K-quant weights multiply with)      // Q8KT: the block-major Q8_K image of a whole ubatch (mmq_tile.hip), not a per-row format
+// block formats whose only kernels of their own are the integer mat-vecs of mmvq.hip (up to 8 columns: Q4_1 / Q5_1 on Q8_1 images, Q2_K / Q3_K on
+// Q8_K images): from 9 columns on every MUL_MAT runs on the F16 image of the weights (resident for model tensors, shadow.hpp, built by the first
+// GEMM; else de-quantised into scratch per call) with f16-rounded activations.  Q2_K / Q3_K share the Q8_K image with the K-quants, but none of
+// the K-quant launch forms (fusions, mmq, the pair / grouped launches, the k_mv2 engine) takes them: those test is_kquant / the type.
 static inline bool is_image_quant(int t) {
     return t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K;
 }
@@ -42,6 +44,7 @@ static inline size_t act_image_bytes(act_kind k, int64_t K) {
     switch (k) {
         case ACT_Q8K: return q8k_image_bytes(K);
         case ACT_Q80: return q80_image_bytes(K);
+        case ACT_Q81: return q81_image_bytes(K);
         case ACT_F16: case ACT_F16Q: return ((size_t) K * 2 + 15) & ~(size_t) 15;
         default: return 0;
     }

@@ -24,9 +24,11 @@ bool supports_op(const ggml_tensor * op) {
             if (s0->nb[0] != type_size(s0->type) || s1->nb[0] != type_size(s1->type) || op->nb[0] != sizeof(float)) return false;
             if (s0->nb[1] < row_size(s0->type, s0->ne[0])) return false;          // transposed weights: not handled
             if (s0->ne[2] == 0 || s0->ne[3] == 0 || s1->ne[2] % s0->ne[2] != 0 || s1->ne[3] % s0->ne[3] != 0) return false;
-            if (k == ACT_Q8K || k == ACT_Q80) {
-                // 16-B / 2-B vector paths assume block-aligned rows (always true for ggml-allocated tensors)
-                if (s0->nb[1] % ((s0->type == GGML_TYPE_Q4_K || s0->type == GGML_TYPE_Q5_K) ? 16 : 2) != 0) return false;
+            if (k == ACT_Q8K || k == ACT_Q80 || k == ACT_Q81) {
+                // 16-B / 4-B / 2-B vector paths assume block-aligned rows (always true for ggml-allocated tensors)
+                const int t = s0->type;
+                const size_t al = (t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K) ? 16 : (t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K) ? 4 : 2;
+                if (s0->nb[1] % al != 0 || (al == 4 && ((uintptr_t) s0->data & 3) != 0)) return false;
             }
             // every mat-vec path (up to 8 columns per launch; F32 weights at any width) stages one activation column in LDS: a column
             // beyond 152 KiB has no kernel (e.g. attention without FLASH_ATTN_EXT past ~77k cache rows: K = n_kv) -> leave it to the CPU
@@ -170,11 +172,15 @@ static const mmv_row MMV_ROWS[] = {
     // IQ4_XS shares the Q8_K image with the K-quants, but none of the K-quant launch forms (fusions, mmq, the k_mv2 engine) takes it: those test is_kquant / the type.
     { GGML_TYPE_IQ4_NL, ACT_Q80, mmv_iq4_nl, "mmv_iq4nl" },
     { GGML_TYPE_IQ4_XS, ACT_Q8K, mmv_iq4_xs, "mmv_iq4xs" },
+    // Q4_1 / Q5_1 (Q8_1 images) and Q2_K / Q3_K (Q8_K images): integer mat-vec kernels up to 8 columns (mmvq.hip), the F16 image from 9 columns on
+    { GGML_TYPE_Q4_1,   ACT_Q81, mmv_q4_1,   "mmv_q41"   },
+    { GGML_TYPE_Q5_1,   ACT_Q81, mmv_q5_1,   "mmv_q51"   },
+    { GGML_TYPE_Q2_K,   ACT_Q8K, mmv_q2_K,   "mmv_q2k"   },
+    { GGML_TYPE_Q3_K,   ACT_Q8K, mmv_q3_K,   "mmv_q3k"   },
     { GGML_TYPE_F16,    ACT_F16, mmv_f16,    "mmv_f16"   },
     { GGML_TYPE_F32,    ACT_F32, mmv_f32,    "mmv_f32"   },
 };
 const mmv_row * mmv_row_for(int wtype) {
-    if (is_image_quant(wtype)) wtype = GGML_TYPE_F16;      // no integer-dot kernels: everything runs on the F16 image, the mat-vec with the F16 row's launcher
     for (const mmv_row & r : MMV_ROWS) if (r.type == wtype) return &r;
     return nullptr;
 }
@@ -269,8 +275,7 @@ mm_route route_mul_mat(const ggml_tensor * n) {
     if ((w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32) && nbatch > 1 && N <= MI_MMVQ_MAX_COLS && nbatch <= 65535 &&
         (r.act != ACT_F32 || x->ne[3] == 1 || x->nb[3] == (size_t) x->ne[2] * x->nb[2])) { r.path = MM_MMV_HEADS; return r; }
     if (mmq_takes(n)) { r.path = MM_MMQ; return r; }                                  // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
-    r.w_image = is_image_quant(w->type);                                              // mat-vec on the F16 image of the block format
-    return r;
+    return r;                                                                         // the type's own mat-vec kernels, on the blocks (w_image only ever with the GEMM)
 }
 bool mm_uses_mmq(const ggml_tensor * n)       { return route_mul_mat(n).path == MM_MMQ; }
 bool mm_uses_mmq_tile(const ggml_tensor * n)  { return route_mul_mat(n).path == MM_MMQ_TILE; }

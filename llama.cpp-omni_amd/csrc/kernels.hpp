@@ -9,6 +9,8 @@ namespace mi {
 // x: [nrows, K] f32 with row stride xs (bytes). img: nrows images of q8k_image_bytes(K) each.
 void quantize_q8k_image(const float * x, size_t xs, void * img, int64_t K, int64_t nrows, hipStream_t st);
 void quantize_q80_image(const float * x, size_t xs, void * img, int64_t K, int64_t nrows, hipStream_t st);
+// Q8_1 image (common.hpp q81_image_bytes): the Q8_0 image plus s = f16(d * sum(qs)) per block -- what Q4_1 / Q5_1 weights multiply with
+void quantize_q81_image(const float * x, size_t xs, void * img, int64_t K, int64_t nrows, hipStream_t st);
 // f32 -> f16 (RNE) rows, dst row stride ys bytes
 void convert_f32_f16_rows(const float * x, size_t xs, uint16_t * y, size_t ys, int64_t K, int64_t nrows, hipStream_t st);
 // f16 rows of the Q8_K-quantised values (d * q, what the reference's integer dot products multiply K-quant weights with): K % 256 == 0; in place for rows a launch left as f16
@@ -42,6 +44,12 @@ void mmv_q5_0(const mmv_args & a, hipStream_t st);
 void mmv_iq4_nl(const mmv_args & a, hipStream_t st);  // IQ4_NL x Q8_0 images / IQ4_XS x Q8_K images (vec_dot_iq4_nl_q8_0 / _iq4_xs_q8_K integers; K % 32 / K % 256 == 0)
 void mmv_iq4_xs(const mmv_args & a, hipStream_t st);
 long mmv_iq4_launches(bool xs);                       // kernel launches so far (stat "mmv_iq4nl_launches" / "mmv_iq4xs_launches")
+void mmv_q4_1(const mmv_args & a, hipStream_t st);    // Q4_1 / Q5_1 x Q8_1 images (vec_dot_q4_1_q8_1 / _q5_1_q8_1 integers; K % 32 == 0, rows 4-byte aligned)
+void mmv_q5_1(const mmv_args & a, hipStream_t st);
+void mmv_q2_K(const mmv_args & a, hipStream_t st);    // Q2_K / Q3_K x Q8_K images (vec_dot_q2_K_q8_K / _q3_K_q8_K integers; K % 256 == 0, rows 4- / 2-byte aligned)
+void mmv_q3_K(const mmv_args & a, hipStream_t st);
+enum { MMV_LOWBIT_Q41 = 0, MMV_LOWBIT_Q51, MMV_LOWBIT_Q2K, MMV_LOWBIT_Q3K };
+long mmv_lowbit_launches(int which);                  // kernel launches so far (stats "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches")
 void mmv_f16 (const mmv_args & a, hipStream_t st);   // act = f16 rows
 void mmv_f32 (const mmv_args & a, hipStream_t st);   // W f32, act = f32 rows
 

@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(256) k_dequant_q80(const char * __restrict__ s
 
 // ---- the other block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q5_K / IQ4_NL / IQ4_XS): one element at a time, the float operations of
 // dequantize_row_q4_0 :307, _q4_1 :327, _q5_0 :348, _q5_1 :374, _q2_K :784, _q3_K :1128, _q5_K :1554, _iq4_nl :2512, _iq4_xs :2530 (ggml-quants.c) in the same order.
-// These types have no integer-dot kernels here: MUL_MAT runs on their (resident) F16 image, GET_ROWS gathers through this function.
+// MUL_MAT from 9 columns on runs on the (resident) F16 image this function fills (mat-vecs read the blocks: mmvq.hip), GET_ROWS gathers through it.
 static __device__ __forceinline__ float h2f_at(const uint8_t * p) { return h2f((uint16_t) (p[0] | (p[1] << 8))); }
 __constant__ int8_t kvalues_iq4nl_dev[16] = { -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 };     // ggml-common.h:1088-1090
 static __device__ float dq_elem_other(int type, const char * row, int64_t e) {

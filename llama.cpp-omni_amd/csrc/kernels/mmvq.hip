@@ -1,4 +1,4 @@
-// mmvq.hip -- weight-streaming mat-vec kernels for Q8_0 / Q4_0 / Q5_0 / IQ4_NL / IQ4_XS / F16 / F32 weights (gfx950, wave64); the K-quants live in mmvk.hip.
+// mmvq.hip -- weight-streaming mat-vec kernels for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_NL / IQ4_XS / F16 / F32 weights (gfx950, wave64); Q4_K / Q5_K / Q6_K live in mmvk.hip.
 //
 // Computes what the reference CPU backend computes in ggml_compute_forward_mul_mat
 // (ggml-cpu/ggml-cpu.c:1210-1402) for ne11 <= 8: every output is one `vec_dot` of a quantised weight
@@ -458,6 +458,348 @@ __global__ void __launch_bounds__(256) k_mmv_iq4xs(const char * __restrict__ W, 
 }
 
 // =================================================================================================
+// Q4_1 / Q5_1 weights x Q8_1 activations.  reference: ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1 (ggml-cpu/arch/x86/quants.c:701-758, :925):
+//   sumi = sum_j (x.qs[j] & 0xF [| fifth bit]) * y.qs[j] + (x.qs[j] >> 4 [| fifth bit]) * y.qs[j + 16]      (quants unsigned: 0..15 / 0..31)
+//   sumf += (d_x * d_y) * sumi + m_x * s_y,      s_y = f16(d_y * sum(y.qs)) from the Q8_1 image (mmv_lds: qs[K] | d[K/32] | s[K/32])
+// Blocks are 20 B {f16 d, f16 m, qs[16]} / 24 B {f16 d, f16 m, u32 qh, qs[16]}: rows and blocks are 4-byte aligned only, so every load is
+// a dword or a dword pair.  Two lanes per block as k_mmv_q40: lane half hf owns qs bytes 8hf .. 8hf+7 = weights 8hf..8hf+7 (low nibbles)
+// and 16+8hf..23+8hf (high) and reads the header dword(s) beside them; half 0 adds the block's m_x * s_y.  32 blocks per wave step, U steps
+// per stage, the next stage requested before the current one is consumed.
+// =================================================================================================
+template <int NCOLS, int ROWS, bool Q5>
+__global__ void __launch_bounds__(256) k_mmv_q41(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
+                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+    typedef u32x2 __attribute__((aligned(4))) u32x2a4;
+    constexpr int BS = Q5 ? 24 : 20, QOFF = Q5 ? 8 : 4;
+    constexpr int U = NCOLS <= 2 ? 2 : 1;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 1, hf = lane & 1;
+    const int nb  = K >> 5;
+    const int nit = (nb + 32 * U - 1) / (32 * U);
+    const size_t img = q81_image_bytes(K);
+    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * 4;
+    const int ngrp   = (nrows + ROWS - 1) / ROWS;
+
+    u32x2 q[U][ROWS]; uint32_t dm[U][ROWS], qh[Q5 ? U : 1][Q5 ? ROWS : 1];
+    auto issue = [&](int grp, int it) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int ib = (it * U + u) * 32 + g; ib = ib < nb ? ib : nb - 1;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
+                const char * bp = W + (size_t) row * w_rs + (size_t) ib * BS;
+                dm[u][r] = *(const uint32_t *) bp;
+                q[u][r]  = *(const u32x2a4 *) (bp + QOFF + 8 * hf);
+                if (Q5) qh[u][r] = *(const uint32_t *) (bp + 4);
+            }
+        }
+    };
+    // fifth bits of 4 consecutive weights (bits b .. b+3 of qh) spread into bit 4 of the four bytes of a word
+    auto spread = [](uint32_t bits) { return ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) << 4; };
+    int grp = wave, it = 0;
+    if (grp < ngrp) issue(grp, 0);
+    stage_act(act, act_cs, NCOLS, img);
+    __syncthreads();
+    if (grp >= ngrp) return;
+
+    float acc[ROWS][NCOLS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
+    while (true) {
+        u32x2 cq[U][ROWS]; uint32_t cd[U][ROWS], ch[Q5 ? U : 1][Q5 ? ROWS : 1];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) { cq[u][r] = q[u][r]; cd[u][r] = dm[u][r]; if (Q5) ch[u][r] = qh[u][r]; }
+        const int cgrp = grp, cit = it;
+        ++it;
+        if (it == nit) { it = 0; grp += nwaves; }
+        const bool more = grp < ngrp;
+        if (more) issue(grp, it);
+
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int  ib    = (cit * U + u) * 32 + g;
+            const bool valid = ib < nb;
+            const int  ibc   = valid ? ib : nb - 1;
+            uint32_t lo[ROWS][2], hi[ROWS][2]; float dx[ROWS], mx[ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                dx[r] = h2f((uint16_t) (cd[u][r] & 0xffffu));
+                mx[r] = hf == 0 ? h2f((uint16_t) (cd[u][r] >> 16)) : 0.0f;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    lo[r][k] = cq[u][r][k] & 0x0f0f0f0fu; hi[r][k] = (cq[u][r][k] >> 4) & 0x0f0f0f0fu;
+                    if (Q5) { lo[r][k] |= spread((ch[u][r] >> (8 * hf + 4 * k)) & 0xfu); hi[r][k] |= spread((ch[u][r] >> (16 + 8 * hf + 4 * k)) & 0xfu); }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NCOLS; ++c) {
+                const char * im = mmv_lds + c * img;
+                const u32x2 a0 = *(const u32x2 *) (im + ibc * 32 + 8 * hf);
+                const u32x2 a1 = *(const u32x2 *) (im + ibc * 32 + 16 + 8 * hf);
+                const float yd = *(const float *) (im + K + ibc * 4);
+                const float ys = *(const float *) (im + K + (nb + ibc) * 4);
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    const bool rv = valid && (cgrp * ROWS + r) < nrows;
+                    const int isum = dot4(lo[r][0], a0[0], dot4(lo[r][1], a0[1], dot4(hi[r][0], a1[0], dot4(hi[r][1], a1[1], 0))));
+                    const float t = (float) isum * (dx[r] * yd) + (hf == 0 ? mx[r] * ys : 0.0f);
+                    acc[r][c] += rv ? t : 0.0f;
+                }
+            }
+        }
+        if (cit == nit - 1) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int row = cgrp * ROWS + r;
+#pragma unroll
+                for (int c = 0; c < NCOLS; ++c) {
+                    const float s = wave_sum_f32(acc[r][c]);
+                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
+                    acc[r][c] = 0.0f;
+                }
+            }
+        }
+        if (!more) break;
+    }
+}
+
+// =================================================================================================
+// Q2_K / Q3_K weights x Q8_K activations (mmv_lds: qs[K] | bsums[K/16] int16 | d[K/256]).  Both formats cut a 256-weight super-block into sixteen
+// 16-weight groups: group k = 8n + 2j + sub covers weights 128n + 32j + 16sub .. +15, whose 2-bit quants are bits 2j, 2j+1 of qs bytes
+// 32n + 16sub .. +15 (dequantize_row_q2_K / _q3_K, ggml-quants.c:784 / :1128) -- bsums[k] of the image is the sum of exactly those activations.
+// Four lanes per super-block: lane quarter qq = 2n + sub owns those 16 qs bytes (one 16-byte load), i.e. the four groups j = 0..3 of its (n, sub);
+// 16 super-blocks per wave step (K = 4096: one step per row), the next row group's loads issued before the current one is consumed.
+//   Q2_K x Q8_K : ggml_vec_dot_q2_K_q8_K (ggml-cpu/arch/x86/quants.c:1277-1353)
+//                 sumf += (d_y * d_x) * sum_k sc_k * sum(q2 * q8) - (d_y * dmin_x) * sum_k m_k * bsums[k],   scales[k] = sc_k | m_k << 4
+//   Q3_K x Q8_K : ggml_vec_dot_q3_K_q8_K (:1469-1587)
+//                 sumf += (d_y * d_x) * sum_k (sc_k - 32) * sum(q3 * q8),   q3 = 2 low bits | hmask bit << 2, minus 4  (the 4 taken out: - 4 * bsums[k])
+// All sums are exact integers; the four lanes of a super-block each convert their quarter, which the reference converts in eight SIMD lanes.
+// =================================================================================================
+// Q2_K: 84-B block {scales[16], qs[64], f16 d, f16 dmin}, 4-byte aligned: the lane reads its 16 qs bytes, the 8 scale bytes of its half n
+// (its own four are bytes 2j + sub of them) and the d / dmin dword.
+template <int NCOLS, int ROWS>
+__global__ void __launch_bounds__(256) k_mmv_q2k(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
+                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+    typedef u32x2 __attribute__((aligned(4))) u32x2a4;
+    typedef u32x4 __attribute__((aligned(4))) u32x4a4;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 2, qq = lane & 3, n = qq >> 1, sub = qq & 1;
+    const int nb  = K >> 8;
+    const int nit = (nb + 15) / 16;
+    const size_t img = q8k_image_bytes(K);
+    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * 4;
+    const int ngrp   = (nrows + ROWS - 1) / ROWS;
+
+    u32x4 q[ROWS]; u32x2 sc[ROWS]; uint32_t dd[ROWS];
+    auto issue = [&](int grp, int it) {
+        int ib = it * 16 + g; ib = ib < nb ? ib : nb - 1;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
+            const char * bp = W + (size_t) row * w_rs + (size_t) ib * 84;
+            sc[r] = *(const u32x2a4 *) (bp + 8 * n);
+            q[r]  = *(const u32x4a4 *) (bp + 16 + 16 * qq);
+            dd[r] = *(const uint32_t *) (bp + 80);
+        }
+    };
+    int grp = wave, it = 0;
+    if (grp < ngrp) issue(grp, 0);
+    stage_act(act, act_cs, NCOLS, img);
+    __syncthreads();
+    if (grp >= ngrp) return;
+
+    float acc[ROWS][NCOLS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
+    while (true) {
+        u32x4 cq[ROWS]; u32x2 cs[ROWS]; uint32_t cd[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) { cq[r] = q[r]; cs[r] = sc[r]; cd[r] = dd[r]; }
+        const int cgrp = grp, cit = it;
+        ++it;
+        if (it == nit) { it = 0; grp += nwaves; }
+        const bool more = grp < ngrp;
+        if (more) issue(grp, it);
+
+        const int  ib    = cit * 16 + g;
+        const bool valid = ib < nb;
+        const int  ibc   = valid ? ib : nb - 1;
+        uint32_t q2[ROWS][4][4]; int scl[ROWS][4], mn[ROWS][4]; float dx[ROWS], dmin[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            dx[r] = h2f((uint16_t) (cd[r] & 0xffffu)); dmin[r] = h2f((uint16_t) (cd[r] >> 16));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t sb = (cs[r][j >> 1] >> (8 * (2 * (j & 1) + sub))) & 0xffu;
+                scl[r][j] = (int) (sb & 0xfu); mn[r][j] = (int) (sb >> 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) q2[r][j][k] = (cq[r][k] >> (2 * j)) & 0x03030303u;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) {
+            const char * im = mmv_lds + c * img;
+            u32x4 a[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = *(const u32x4 *) (im + (size_t) ibc * 256 + 128 * n + 32 * j + 16 * sub);
+            const u32x4 bs = *(const u32x4 *) (im + K + ibc * 32 + 16 * n);          // bsums[8n .. 8n+7]: group j of this lane is element 2j + sub
+            const float yd = *(const float *) (im + K + K / 8 + ibc * 4);
+            int bsum[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bsum[j] = ((int) (bs[j] << (16 - 16 * sub))) >> 16;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const bool rv = valid && (cgrp * ROWS + r) < nrows;
+                int isum = 0, msum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int s = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s = dot4(q2[r][j][k], a[j][k], s);
+                    isum += scl[r][j] * s;
+                    msum += mn[r][j] * bsum[j];
+                }
+                const float t = (yd * dx[r]) * (float) isum - (yd * dmin[r]) * (float) msum;
+                acc[r][c] += rv ? t : 0.0f;
+            }
+        }
+        if (cit == nit - 1) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int row = cgrp * ROWS + r;
+#pragma unroll
+                for (int c = 0; c < NCOLS; ++c) {
+                    const float s = wave_sum_f32(acc[r][c]);
+                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
+                    acc[r][c] = 0.0f;
+                }
+            }
+        }
+        if (!more) break;
+    }
+}
+
+// Q3_K: 110-B block {hmask[32], qs[64], scales[12], f16 d}, 2-byte aligned only (110 = 2 * 55): no field of a block has a fixed dword phase, so
+// the lane mapping is built on three 16-byte loads that the hardware takes at any 2-byte address and that all stay inside the block --
+//   hmask bytes 16sub .. +15 (bit 4n + j of byte l is the high bit of group j's weight l), qs bytes 16qq .. +15, and bytes 94 .. 109:
+//   the last two qs bytes (unused), the 12 scale bytes and d -- a 16-byte load at 96 would run two bytes past the tensor's last block.
+// The 6-bit scales are unpacked as the reference does (kmask1 / kmask2 on three dwords): scale k is byte k & 3 of word k >> 2.
+template <int NCOLS, int ROWS>
+__global__ void __launch_bounds__(256) k_mmv_q3k(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
+                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+    typedef u32x4 __attribute__((aligned(2))) u32x4a2;
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 2, qq = lane & 3, n = qq >> 1, sub = qq & 1;
+    const int nb  = K >> 8;
+    const int nit = (nb + 15) / 16;
+    const size_t img = q8k_image_bytes(K);
+    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * 4;
+    const int ngrp   = (nrows + ROWS - 1) / ROWS;
+
+    u32x4 hm[ROWS], q[ROWS], hd[ROWS];
+    auto issue = [&](int grp, int it) {
+        int ib = it * 16 + g; ib = ib < nb ? ib : nb - 1;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
+            const char * bp = W + (size_t) row * w_rs + (size_t) ib * 110;
+            hm[r] = *(const u32x4a2 *) (bp + 16 * sub);
+            q[r]  = *(const u32x4a2 *) (bp + 32 + 16 * qq);
+            hd[r] = *(const u32x4a2 *) (bp + 94);
+        }
+    };
+    int grp = wave, it = 0;
+    if (grp < ngrp) issue(grp, 0);
+    stage_act(act, act_cs, NCOLS, img);
+    __syncthreads();
+    if (grp >= ngrp) return;
+
+    float acc[ROWS][NCOLS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
+    while (true) {
+        u32x4 chm[ROWS], cq[ROWS], chd[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) { chm[r] = hm[r]; cq[r] = q[r]; chd[r] = hd[r]; }
+        const int cgrp = grp, cit = it;
+        ++it;
+        if (it == nit) { it = 0; grp += nwaves; }
+        const bool more = grp < ngrp;
+        if (more) issue(grp, it);
+
+        const int  ib    = cit * 16 + g;
+        const bool valid = ib < nb;
+        const int  ibc   = valid ? ib : nb - 1;
+        uint32_t q3[ROWS][4][4]; int scl[ROWS][4]; float dx[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const uint32_t aux0 = (chd[r][0] >> 16) | (chd[r][1] << 16), aux1 = (chd[r][1] >> 16) | (chd[r][2] << 16), aux2 = (chd[r][2] >> 16) | (chd[r][3] << 16);
+            dx[r] = h2f((uint16_t) (chd[r][3] >> 16));
+            // words 2n and 2n + 1 of the reference's scales128: scales 8n .. 8n+3 and 8n+4 .. 8n+7
+            const uint32_t sa = ((aux0 >> (4 * n)) & 0x0f0f0f0fu) | (((aux2 >> (4 * n)) & 0x03030303u) << 4);
+            const uint32_t sb = ((aux1 >> (4 * n)) & 0x0f0f0f0fu) | (((aux2 >> (4 * n + 2)) & 0x03030303u) << 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                scl[r][j] = (int) (((j < 2 ? sa : sb) >> (8 * (2 * (j & 1) + sub))) & 0xffu) - 32;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) q3[r][j][k] = ((cq[r][k] >> (2 * j)) & 0x03030303u) | (((chm[r][k] >> (4 * n + j)) & 0x01010101u) << 2);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NCOLS; ++c) {
+            const char * im = mmv_lds + c * img;
+            u32x4 a[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = *(const u32x4 *) (im + (size_t) ibc * 256 + 128 * n + 32 * j + 16 * sub);
+            const u32x4 bs = *(const u32x4 *) (im + K + ibc * 32 + 16 * n);          // bsums[8n .. 8n+7]: group j of this lane is element 2j + sub
+            const float yd = *(const float *) (im + K + K / 8 + ibc * 4);
+            int bsum[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bsum[j] = ((int) (bs[j] << (16 - 16 * sub))) >> 16;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const bool rv = valid && (cgrp * ROWS + r) < nrows;
+                int isum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    int s = -4 * bsum[j];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s = dot4(q3[r][j][k], a[j][k], s);
+                    isum += scl[r][j] * s;
+                }
+                const float t = (yd * dx[r]) * (float) isum;
+                acc[r][c] += rv ? t : 0.0f;
+            }
+        }
+        if (cit == nit - 1) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int row = cgrp * ROWS + r;
+#pragma unroll
+                for (int c = 0; c < NCOLS; ++c) {
+                    const float s = wave_sum_f32(acc[r][c]);
+                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
+                    acc[r][c] = 0.0f;
+                }
+            }
+        }
+        if (!more) break;
+    }
+}
+
+// =================================================================================================
 // F16 / F32 weights: each lane consumes 16 B (8 halfs / 4 floats) per step; activations (f16 rows for F16
 // weights, as the reference rounds src1 to the F16 vec_dot_type; f32 rows for F32 weights) live in LDS.
 // =================================================================================================
@@ -752,6 +1094,40 @@ static void mmv_iq4_t(const mmv_args & a0, hipStream_t st) {
 }
 void mmv_iq4_nl(const mmv_args & a, hipStream_t st) { mmv_iq4_t<false>(a, st); }
 void mmv_iq4_xs(const mmv_args & a, hipStream_t st) { mmv_iq4_t<true>(a, st); }
+
+// Q4_1 / Q5_1 (Q8_1 images) and Q2_K / Q3_K (Q8_K images): one launch per call of up to 8 columns, counted per type
+static long g_lowbit_launches[4] = { 0, 0, 0, 0 };
+long mmv_lowbit_launches(int which) { return which >= 0 && which < 4 ? g_lowbit_launches[which] : 0; }
+#define MMV_LOWBIT_PICK(KERNEL, ...)                                     \
+    switch (a.ncols) {                                                   \
+        case 1: k = KERNEL<1, 2, ##__VA_ARGS__>; break;                  \
+        case 2: k = KERNEL<2, 2, ##__VA_ARGS__>; break;                  \
+        case 3: k = KERNEL<3, 2, ##__VA_ARGS__>; break;                  \
+        case 4: k = KERNEL<4, 2, ##__VA_ARGS__>; break;                  \
+        case 5: k = KERNEL<5, 1, ##__VA_ARGS__>; rows = 1; break;        \
+        case 6: k = KERNEL<6, 1, ##__VA_ARGS__>; rows = 1; break;        \
+        case 7: k = KERNEL<7, 1, ##__VA_ARGS__>; rows = 1; break;        \
+        case 8: k = KERNEL<8, 1, ##__VA_ARGS__>; rows = 1; break;        \
+        default: abort();                                                \
+    }
+template <int WHICH>
+static void mmv_lowbit_t(const mmv_args & a0, hipStream_t st) {
+    if (a0.nrows == 0 || a0.ncols == 0) return;
+    const size_t ib = (WHICH == MMV_LOWBIT_Q41 || WHICH == MMV_LOWBIT_Q51) ? q81_image_bytes(a0.K) : q8k_image_bytes(a0.K);
+    split_cols(a0, ib, [&](const mmv_args & a) {
+        mmv_kernel_t k = nullptr; int rows = 2;
+        if      (WHICH == MMV_LOWBIT_Q41) { MMV_LOWBIT_PICK(k_mmv_q41, false) }
+        else if (WHICH == MMV_LOWBIT_Q51) { MMV_LOWBIT_PICK(k_mmv_q41, true) }
+        else if (WHICH == MMV_LOWBIT_Q2K) { MMV_LOWBIT_PICK(k_mmv_q2k) }
+        else                              { MMV_LOWBIT_PICK(k_mmv_q3k) }
+        launch_mmv(k, rows, ib * a.ncols, a, st);
+        ++g_lowbit_launches[WHICH];
+    });
+}
+void mmv_q4_1(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q41>(a, st); }
+void mmv_q5_1(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q51>(a, st); }
+void mmv_q2_K(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q2K>(a, st); }
+void mmv_q3_K(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q3K>(a, st); }
 
 #define MMVF_LAUNCH(NC, ROWS, WF16)                                                                                    \
     do {                                                                                                               \

@@ -118,6 +118,42 @@ void quantize_q80_image(const float * x, size_t xs, void * img, int64_t K, int64
 }
 
 // ------------------------------------------------------------------------------------------------
+// Q8_1 image (Q4_1 / Q5_1 weights).  32 lanes per block, as above.
+//   reference: quantize_row_q8_1, ggml-cpu/arch/x86/quants.c:388-455 (AVX2 form): qs and d as quantize_row_q8_0, and
+//     s  = f16(d * (float) sum(q))      with d the unrounded f32 amax / 127 and the sum taken in integers
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_quantize_q81(const char * __restrict__ x, size_t xs, char * __restrict__ img,
+                                                     int64_t K, int64_t nrows, size_t img_bytes) {
+    const int64_t nb  = K / 32;
+    const int64_t blk = (int64_t) blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (blk >= nb * nrows) return;
+    const int     l   = threadIdx.x & 31;
+    const int64_t row = blk / nb, ib = blk % nb;
+    const float   v   = ((const float *) (x + row * xs))[ib * 32 + l];
+    float amax = fabsf(v);
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const float d  = amax / 127.0f;
+    const float id = amax != 0.0f ? 127.0f / amax : 0.0f;
+    const int   q  = (int) __builtin_rintf(v * id);
+    int sum = q;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) sum += __shfl_xor(sum, o, 64);
+    char * im = img + row * img_bytes;
+    ((int8_t *) im)[ib * 32 + l] = (int8_t) q;
+    if (l == 0) {
+        ((float *) (im + K))[ib]      = h2f(f2h(d));
+        ((float *) (im + K))[nb + ib] = h2f(f2h(d * (float) sum));
+    }
+}
+
+void quantize_q81_image(const float * x, size_t xs, void * img, int64_t K, int64_t nrows, hipStream_t st) {
+    const int64_t nblk = K / 32 * nrows;
+    if (nblk == 0) return;
+    k_quantize_q81<<<dim3((unsigned) ((nblk + 7) / 8)), dim3(256), 0, st>>>((const char *) x, xs, (char *) img, K, nrows, q81_image_bytes(K));
+}
+
+// ------------------------------------------------------------------------------------------------
 // f32 -> f16 rows (RNE), the F16 weights' vec_dot_type conversion (ggml_cpu_fp32_to_fp16)
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_f32_to_f16_rows(const char * __restrict__ x, size_t xs, char * __restrict__ y, size_t ys, int64_t K, int64_t nrows) {

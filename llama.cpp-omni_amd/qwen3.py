@@ -132,6 +132,29 @@ def random_blocks(rng, ty, nrows, K, std=0.02):
         blk[..., 0:2] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
         blk[..., 2:] = rng.integers(0, 256, size=(nrows, nb, 134), dtype=np.uint8)     # scales_h, scales_l[4], qs[128]
         return blk.reshape(nrows, nb * 136)
+    if ty in (3, 7):                                         # Q4_1 / Q5_1: value = d * q + m, q in [0, 15] / [0, 31]: std ~ 4.6 d / 9.2 d; m a small positive offset
+        nb, bs = K // 32, (20 if ty == 3 else 24)
+        blk = np.empty((nrows, nb, bs), dtype=np.uint8)
+        d = (std / (4.6 if ty == 3 else 9.2)) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., 0:2] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        blk[..., 2:4] = _f16_bits(d * 0.5)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        blk[..., 4:] = rng.integers(0, 256, size=(nrows, nb, bs - 4), dtype=np.uint8)      # [qh,] qs[16]
+        return blk.reshape(nrows, nb * bs)
+    if ty == 10:                                             # Q2_K: value = d*sc*q - dmin*m, sc, m in [0, 15], q in [0, 3]: E[sc*q] = 11.25, E[m] = 7.5, std ~ 13.9 d at dmin = 1.5 d
+        nb = K // 256
+        blk = np.empty((nrows, nb, 84), dtype=np.uint8)
+        d = (std / 13.9) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., :80] = rng.integers(0, 256, size=(nrows, nb, 80), dtype=np.uint8)         # scales[16], qs[64]
+        blk[..., 80:82] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        blk[..., 82:84] = _f16_bits(d * 1.5)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        return blk.reshape(nrows, nb * 84)
+    if ty == 11:                                             # Q3_K: value = d * (sc - 32) * (q - 4 or q), sc in [0, 63], q in [0, 3]: std ~ 18.5 * 2.3 = 43 d
+        nb = K // 256
+        blk = np.empty((nrows, nb, 110), dtype=np.uint8)
+        d = (std / 43.0) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., :108] = rng.integers(0, 256, size=(nrows, nb, 108), dtype=np.uint8)       # hmask[32], qs[64], scales[12]
+        blk[..., 108:110] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        return blk.reshape(nrows, nb * 110)
     raise ValueError(ty)
 
 

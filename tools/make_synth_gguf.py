@@ -168,7 +168,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=["8b", "tiny", "tts", "tts-tiny"], default="8b",
                     help="8b / tiny: qwen3 arch; tts / tts-tiny: the omni TTS decoder's shape (arch llama, RoPE NORM, no q/k-norm; SURVEY.md 8(f) rank 2)")
-    ap.add_argument("--types", choices=["q4_k_m", "f16", "q8_0", "q4_0", "q5_k", "iq4_xs", "iq4_nl"], default="q4_k_m")
+    ap.add_argument("--types", choices=["q4_k_m", "f16", "q8_0", "q4_0", "q5_k", "iq4_xs", "iq4_nl", "q4_1", "q5_1", "q2_k", "q3_k"], default="q4_k_m")
     ap.add_argument("-o", "--out", required=True)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--distinct-layers", action="store_true", help="fresh random bytes per layer (small configs)")
@@ -206,6 +206,9 @@ def main():
         types, embd_ty, ftype = qwen3.iq4_xs_types(cfg), 23, 30                     # GGML_TYPE_IQ4_XS, LLAMA_FTYPE_MOSTLY_IQ4_XS (include/llama.h:145)
     elif args.types == "iq4_nl":
         types, embd_ty, ftype = qwen3.iq4_xs_types(cfg, 20), 20, 25                 # GGML_TYPE_IQ4_NL, LLAMA_FTYPE_MOSTLY_IQ4_NL (include/llama.h:140)
+    elif args.types in ("q4_1", "q5_1", "q2_k", "q3_k"):                                # uniform files; LLAMA_FTYPE_MOSTLY_Q4_1 / _Q5_1 / _Q2_K / _Q3_K_S (include/llama.h:118-126)
+        ty, ftype = {"q4_1": (3, 3), "q5_1": (7, 9), "q2_k": (10, 10), "q3_k": (11, 11)}[args.types]
+        types, embd_ty = qwen3.uniform_types(cfg, ty), ty
     else:
         types, embd_ty, ftype = qwen3.uniform_types(cfg, GGML_TYPE_Q8_0), GGML_TYPE_Q8_0, 7
     E, H, HK, D, F, V, L = cfg["n_embd"], cfg["n_head"], cfg["n_head_kv"], cfg["head_dim"], cfg["n_ff"], cfg["n_vocab"], cfg["n_layer"]
