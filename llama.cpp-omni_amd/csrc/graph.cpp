@@ -403,12 +403,12 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "attn_vrows_launches")) return (double) mi::attn_vrows_launches();
     if (!strcmp(key, "fattn_gs_launches"))  return (double) mi::fattn_gs_launches();
     if (!strcmp(key, "fattn_gs_far_launches")) return (double) mi::fattn_gs_far_launches();
-    if (!strcmp(key, "mmv_iq4nl_launches")) return (double) mi::mmv_iq4_launches(false);
-    if (!strcmp(key, "mmv_iq4xs_launches")) return (double) mi::mmv_iq4_launches(true);
-    if (!strcmp(key, "mmv_q41_launches"))   return (double) mi::mmv_lowbit_launches(mi::MMV_LOWBIT_Q41);
-    if (!strcmp(key, "mmv_q51_launches"))   return (double) mi::mmv_lowbit_launches(mi::MMV_LOWBIT_Q51);
-    if (!strcmp(key, "mmv_q2k_launches"))   return (double) mi::mmv_lowbit_launches(mi::MMV_LOWBIT_Q2K);
-    if (!strcmp(key, "mmv_q3k_launches"))   return (double) mi::mmv_lowbit_launches(mi::MMV_LOWBIT_Q3K);
+    if (!strcmp(key, "mmv_iq4nl_launches")) return (double) mi::mmv_blocks_launches(mi::MMV_FORM_IQ4_NL);
+    if (!strcmp(key, "mmv_iq4xs_launches")) return (double) mi::mmv_blocks_launches(mi::MMV_FORM_IQ4_XS);
+    if (!strcmp(key, "mmv_q41_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q4_1);
+    if (!strcmp(key, "mmv_q51_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q5_1);
+    if (!strcmp(key, "mmv_q2k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q2_K);
+    if (!strcmp(key, "mmv_q3k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q3_K);
     if (!strncmp(key, "prof_", 5)) {
         std::string k(key + 5);
         const size_t us = k.rfind("_us"), nn = k.rfind("_n"), by = k.rfind("_bytes");

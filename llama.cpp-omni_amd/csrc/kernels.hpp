@@ -43,13 +43,14 @@ void mmv_q4_0(const mmv_args & a, hipStream_t st);   // Q4_0 / Q5_0 weights x Q8
 void mmv_q5_0(const mmv_args & a, hipStream_t st);
 void mmv_iq4_nl(const mmv_args & a, hipStream_t st);  // IQ4_NL x Q8_0 images / IQ4_XS x Q8_K images (vec_dot_iq4_nl_q8_0 / _iq4_xs_q8_K integers; K % 32 / K % 256 == 0)
 void mmv_iq4_xs(const mmv_args & a, hipStream_t st);
-long mmv_iq4_launches(bool xs);                       // kernel launches so far (stat "mmv_iq4nl_launches" / "mmv_iq4xs_launches")
 void mmv_q4_1(const mmv_args & a, hipStream_t st);    // Q4_1 / Q5_1 x Q8_1 images (vec_dot_q4_1_q8_1 / _q5_1_q8_1 integers; K % 32 == 0, rows 4-byte aligned)
 void mmv_q5_1(const mmv_args & a, hipStream_t st);
 void mmv_q2_K(const mmv_args & a, hipStream_t st);    // Q2_K / Q3_K x Q8_K images (vec_dot_q2_K_q8_K / _q3_K_q8_K integers; K % 256 == 0, rows 4- / 2-byte aligned)
 void mmv_q3_K(const mmv_args & a, hipStream_t st);
-enum { MMV_LOWBIT_Q41 = 0, MMV_LOWBIT_Q51, MMV_LOWBIT_Q2K, MMV_LOWBIT_Q3K };
-long mmv_lowbit_launches(int which);                  // kernel launches so far (stats "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches")
+// the nine block formats above share one kernel frame (mmvq.hip); kernel launches so far per form (stats "mmv_iq4nl_launches", "mmv_iq4xs_launches",
+// "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches")
+enum { MMV_FORM_Q8_0 = 0, MMV_FORM_Q4_0, MMV_FORM_Q5_0, MMV_FORM_IQ4_NL, MMV_FORM_IQ4_XS, MMV_FORM_Q4_1, MMV_FORM_Q5_1, MMV_FORM_Q2_K, MMV_FORM_Q3_K, MMV_FORM_COUNT };
+long mmv_blocks_launches(int form);
 void mmv_f16 (const mmv_args & a, hipStream_t st);   // act = f16 rows
 void mmv_f32 (const mmv_args & a, hipStream_t st);   // W f32, act = f32 rows
 

@@ -33,41 +33,47 @@ static __device__ __forceinline__ void stage_act(const char * act, size_t act_cs
 }
 
 // =================================================================================================
-// Q8_0 : 34-B block {f16 d, int8 qs[32]} (ggml-common.h:219-224).  8 lanes per block (4 bytes each);
-// a wave covers 8 blocks (272 B) per step.  Activation image: qs[K] int8 + per-32 f32 scale.
-//   sumf += sumi * (d_x * d_y)   (ggml-cpu/quants.c:318-327)
+// The block formats share one kernel frame, k_mmv_blocks<Form, NCOLS, ROWS>.  A wave walks the row groups wave, wave + nwaves, ... of ROWS
+// rows each; in one step its 64 lanes cover 64 / Form::LANES blocks of every row of the group (lane = block g, part `part` of that block),
+// U steps make a stage.  The frame owns the bookkeeping, the clamps that keep every load in bounds, the barrier, the stage pipeline, the
+// masking of out-of-range lanes and rows, and the reduction and store at the end of a row group.  A Form supplies what differs:
+//   LANES, BYTES, LOG2W, ID    lanes per block, bytes per block, log2 of the weights per block, slot of the launch counter
+//   U(ncols)                   steps per stage
+//   image_bytes(K)             size of one activation image (Q8_0 / Q8_1 / Q8_K)
+//   regs,  load(bp, part)      what a lane holds in flight for one row of one step, and the loads of block `bp` that fill it
+//   row,   decode(regs, part)  the weights as the dot products take them: once per (step, row), not per column
+//   col,   read(im, ib, part, K, nb)   the lane's part of block ib of one image: once per (step, column), not per row
+//   term(row, col, part)       the f32 contribution of the block part to the output; the frame masks and adds it
+//   reduce(v)                  the wave sum.  wave_sum (six shuffles, a butterfly) and wave_sum_f32 (DPP rows, then row broadcasts) add in
+//                              different orders, so their f32 results differ in the last bit: each form keeps the one it was written with.
 // =================================================================================================
-template <int NCOLS, int ROWS>
-__global__ void __launch_bounds__(256) k_mmv_q80(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
-    // four lanes per 34-byte block (8 quants = one hardware-unaligned 8-byte load each; blocks are only 2-byte aligned), 16 blocks per
-    // wave step, U steps per stage; the loads of the next stage are issued before the current one is consumed, the first ones before
-    // the activation images are staged
-    typedef u32x2 __attribute__((aligned(2))) u32x2a2;
-    constexpr int U = NCOLS <= 2 ? 4 : 2;
+template <class Form, int NCOLS, int ROWS>
+__global__ void __launch_bounds__(256) k_mmv_blocks(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
+                                                   char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+    constexpr int U = Form::U(NCOLS), BPS = 64 / Form::LANES;                 // blocks per wave step
     const int lane = threadIdx.x & 63;
-    const int g = lane >> 2, lp = lane & 3;
-    const int nb  = K >> 5;
-    const int nit = (nb + 16 * U - 1) / (16 * U);
-    const size_t img = q80_image_bytes(K);
+    const int g = lane / Form::LANES, part = lane % Form::LANES;
+    const int nb  = K >> Form::LOG2W;
+    const int nit = (nb + BPS * U - 1) / (BPS * U);
+    const size_t img = Form::image_bytes(K);
     const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * 4;
     const int ngrp   = (nrows + ROWS - 1) / ROWS;
 
-    u32x2 q[U][ROWS]; uint32_t dw[U][ROWS];
+    // no bounds branch around a load: block index and row are clamped, the contribution is zeroed when it is consumed
+    typename Form::regs q[U][ROWS];
     auto issue = [&](int grp, int it) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            int ib = (it * U + u) * 16 + g; ib = ib < nb ? ib : nb - 1;
+            int ib = (it * U + u) * BPS + g; ib = ib < nb ? ib : nb - 1;
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
                 int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-                const char * bp = W + (size_t) row * w_rs + (size_t) ib * 34;
-                dw[u][r] = *(const uint16_t *) bp;
-                q[u][r]  = *(const u32x2a2 *) (bp + 2 + 8 * lp);
+                q[u][r] = Form::load(W + (size_t) row * w_rs + (size_t) ib * Form::BYTES, part);
             }
         }
     };
+    // the first stage is requested before the activation images are staged; every wave reaches the barrier before any returns
     int grp = wave, it = 0;
     if (grp < ngrp) issue(grp, 0);
     stage_act(act, act_cs, NCOLS, img);
@@ -80,11 +86,12 @@ __global__ void __launch_bounds__(256) k_mmv_q80(const char * __restrict__ W, si
 #pragma unroll
         for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
     while (true) {
-        u32x2 cq[U][ROWS]; uint32_t cd[U][ROWS];
+        // the registers in flight are copied, then the next stage (of this row group or of the wave's next one) is requested
+        typename Form::regs cq[U][ROWS];
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) { cq[u][r] = q[u][r]; cd[u][r] = dw[u][r]; }
+            for (int r = 0; r < ROWS; ++r) cq[u][r] = q[u][r];
         const int cgrp = grp, cit = it;
         ++it;
         if (it == nit) { it = 0; grp += nwaves; }
@@ -93,18 +100,19 @@ __global__ void __launch_bounds__(256) k_mmv_q80(const char * __restrict__ W, si
 
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int  ib    = (cit * U + u) * 16 + g;
+            const int  ib    = (cit * U + u) * BPS + g;
             const bool valid = ib < nb;
             const int  ibc   = valid ? ib : nb - 1;
+            typename Form::row w[ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) w[r] = Form::decode(cq[u][r], part);
 #pragma unroll
             for (int c = 0; c < NCOLS; ++c) {
-                const char * im = mmv_lds + c * img;
-                const u32x2 a  = *(const u32x2 *) (im + ibc * 32 + 8 * lp);
-                const float yd = *(const float *) (im + K + ibc * 4);
+                const typename Form::col y = Form::read(mmv_lds + c * img, ibc, part, K, nb);
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r) {
                     const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                    const float t = (float) dot4(cq[u][r][0], a[0], dot4(cq[u][r][1], a[1], 0)) * (h2f((uint16_t) cd[u][r]) * yd);
+                    const float t = Form::term(w[r], y, part);
                     acc[r][c] += rv ? t : 0.0f;
                 }
             }
@@ -115,7 +123,7 @@ __global__ void __launch_bounds__(256) k_mmv_q80(const char * __restrict__ W, si
                 const int row = cgrp * ROWS + r;
 #pragma unroll
                 for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum(acc[r][c]);
+                    const float s = Form::reduce(acc[r][c]);
                     if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
                     acc[r][c] = 0.0f;
                 }
@@ -123,119 +131,110 @@ __global__ void __launch_bounds__(256) k_mmv_q80(const char * __restrict__ W, si
         }
         if (!more) break;
     }
+}
+
+// =================================================================================================
+// Q8_0 : 34-B block {f16 d, int8 qs[32]} (ggml-common.h:219-224).  Activation image: qs[K] int8 + per-32 f32 scale.
+//   sumf += sumi * (d_x * d_y)   (ggml-cpu/quants.c:318-327)
+// Four lanes per 34-byte block (8 quants = one hardware-unaligned 8-byte load each; blocks are only 2-byte aligned), 16 blocks per
+// wave step, U steps per stage.
+// =================================================================================================
+struct q80_form {
+    static constexpr int LANES = 4, BYTES = 34, LOG2W = 5, ID = MMV_FORM_Q8_0;
+    static constexpr int U(int ncols) { return ncols <= 2 ? 4 : 2; }
+    MI_HD static size_t image_bytes(int64_t K) { return q80_image_bytes(K); }
+    typedef u32x2 __attribute__((aligned(2))) u32x2a2;
+    struct regs { u32x2 q; uint32_t dw; };
+    struct row  { u32x2 q; float dx; };
+    struct col  { u32x2 a; float yd; };
+    static __device__ __forceinline__ regs load(const char * bp, int lp) {
+        regs x;
+        x.dw = *(const uint16_t *) bp;
+        x.q  = *(const u32x2a2 *) (bp + 2 + 8 * lp);
+        return x;
+    }
+    static __device__ __forceinline__ row decode(const regs & x, int) { return { x.q, h2f((uint16_t) x.dw) }; }
+    static __device__ __forceinline__ col read(const char * im, int ib, int lp, int K, int) {
+        col y;
+        y.a  = *(const u32x2 *) (im + ib * 32 + 8 * lp);
+        y.yd = *(const float *) (im + K + ib * 4);
+        return y;
+    }
+    static __device__ __forceinline__ float term(const row & w, const col & y, int) { return (float) dot4(w.q[0], y.a[0], dot4(w.q[1], y.a[1], 0)) * (w.dx * y.yd); }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum(v); }
+};
+
+// ---- shared by the five nibble forms of 32-weight blocks (Q4_0 / Q5_0 / IQ4_NL / Q4_1 / Q5_1).  Two lanes per block: lane half hf owns nibble
+// bytes 8hf .. 8hf+7 = weights 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high); 32 blocks per wave step, U steps per stage.
+template <bool Q5> struct qh_word { uint32_t qh; };            // the fifth bits of a Q5_0 / Q5_1 block: a member of `regs` only where the format has them
+template <> struct qh_word<false> {};
+// fifth bits of 4 consecutive weights (bits b .. b+3 of qh) spread into bit 4 of the four bytes of a word
+static __device__ __forceinline__ uint32_t spread5(uint32_t bits) { return ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) << 4; }
+struct nib_quants { uint32_t lo[2], hi[2]; };                   // the lane's 16 quants, one per byte
+template <bool Q5>
+static __device__ __forceinline__ nib_quants nib_unpack(u32x2 q, uint32_t qh, int hf) {
+    nib_quants n;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        n.lo[k] = q[k] & 0x0f0f0f0fu; n.hi[k] = (q[k] >> 4) & 0x0f0f0f0fu;
+        if (Q5) { n.lo[k] |= spread5((qh >> (8 * hf + 4 * k)) & 0xfu); n.hi[k] |= spread5((qh >> (16 + 8 * hf + 4 * k)) & 0xfu); }
+    }
+    return n;
+}
+struct nib_act { u32x2 a0, a1; float yd; };                     // the activations under the lane's low and high nibbles, and the block's scale
+static __device__ __forceinline__ nib_act nib_read(const char * im, int ib, int hf, int K) {
+    nib_act y;
+    y.a0 = *(const u32x2 *) (im + ib * 32 + 8 * hf);
+    y.a1 = *(const u32x2 *) (im + ib * 32 + 16 + 8 * hf);
+    y.yd = *(const float *) (im + K + ib * 4);
+    return y;
+}
+static __device__ __forceinline__ int nib_dot(const nib_quants & n, const nib_act & y) {
+    return dot4(n.lo[0], y.a0[0], dot4(n.lo[1], y.a0[1], dot4(n.hi[0], y.a1[0], dot4(n.hi[1], y.a1[1], 0))));
 }
 
 // =================================================================================================
 // Q4_0 / Q5_0 weights x Q8_0 activations.  reference: ggml_vec_dot_q4_0_q8_0 / _q5_0_q8_0 (ggml-cpu/quants.c:115-149, 219-262):
 //   sumi = sum_j ((x.qs[j] & 0xF) [| fifth bit] - OFF) * y.qs[j] + ((x.qs[j] >> 4) [| fifth bit] - OFF) * y.qs[j + 16],  OFF = 8 / 16
 //   sumf += sumi * d_x * d_y
-// Four lanes per 32-weight block (4 bytes of nibbles = weights 4l..4l+3 and 16+4l..19+4l each), 16 blocks per wave step; the offset is
-// taken out of the dot products (sum q*y - OFF * sum y), all in exact integers.
+// Blocks are 18 B {f16 d, qs[16]} / 22 B {f16 d, u32 qh, qs[16]}, 2-byte aligned.  Two lanes per block (see above); the offset is taken out of
+// the dot products (sum q*y - OFF * sum y), all in exact integers.
 // =================================================================================================
-template <int NCOLS, int ROWS, bool Q5>
-__global__ void __launch_bounds__(256) k_mmv_q40(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
-    // two lanes per block: lane half hf owns nibble bytes 8hf .. 8hf+7 = weights 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high);
-    // 32 blocks per wave step, U steps per stage, next stage requested before the current one is consumed
+template <bool Q5>
+struct q40_form {
+    static constexpr int LANES = 2, BYTES = Q5 ? 22 : 18, LOG2W = 5, ID = Q5 ? MMV_FORM_Q5_0 : MMV_FORM_Q4_0;
+    static constexpr int QOFF = Q5 ? 6 : 2, OFF = Q5 ? 16 : 8;
+    static constexpr int U(int ncols) { return ncols <= 2 ? 2 : 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q80_image_bytes(K); }
     typedef u32x2 __attribute__((aligned(2))) u32x2a2;
     typedef uint32_t __attribute__((aligned(2))) u32a2;
-    constexpr int BS = Q5 ? 22 : 18, QOFF = Q5 ? 6 : 2, OFF = Q5 ? 16 : 8;
-    constexpr int U = NCOLS <= 2 ? 2 : 1;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 1, hf = lane & 1;
-    const int nb  = K >> 5;
-    const int nit = (nb + 32 * U - 1) / (32 * U);
-    const size_t img = q80_image_bytes(K);
-    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * 4;
-    const int ngrp   = (nrows + ROWS - 1) / ROWS;
-
-    u32x2 q[U][ROWS]; uint32_t dw[U][ROWS], qh[Q5 ? U : 1][Q5 ? ROWS : 1];
-    auto issue = [&](int grp, int it) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int ib = (it * U + u) * 32 + g; ib = ib < nb ? ib : nb - 1;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-                const char * bp = W + (size_t) row * w_rs + (size_t) ib * BS;
-                dw[u][r] = *(const uint16_t *) bp;
-                q[u][r]  = *(const u32x2a2 *) (bp + QOFF + 8 * hf);
-                if (Q5) qh[u][r] = *(const u32a2 *) (bp + 2);
-            }
-        }
-    };
-    // fifth bits of 4 consecutive weights (bits b .. b+3 of qh) spread into bit 4 of the four bytes of a word
-    auto spread = [](uint32_t bits) { return ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) << 4; };
-    int grp = wave, it = 0;
-    if (grp < ngrp) issue(grp, 0);
-    stage_act(act, act_cs, NCOLS, img);
-    __syncthreads();
-    if (grp >= ngrp) return;
-
-    float acc[ROWS][NCOLS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
-    while (true) {
-        u32x2 cq[U][ROWS]; uint32_t cd[U][ROWS], ch[Q5 ? U : 1][Q5 ? ROWS : 1];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) { cq[u][r] = q[u][r]; cd[u][r] = dw[u][r]; if (Q5) ch[u][r] = qh[u][r]; }
-        const int cgrp = grp, cit = it;
-        ++it;
-        if (it == nit) { it = 0; grp += nwaves; }
-        const bool more = grp < ngrp;
-        if (more) issue(grp, it);
-
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int  ib    = (cit * U + u) * 32 + g;
-            const bool valid = ib < nb;
-            const int  ibc   = valid ? ib : nb - 1;
-            uint32_t lo[ROWS][2], hi[ROWS][2]; float dx[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                dx[r] = h2f((uint16_t) cd[u][r]);
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    lo[r][k] = cq[u][r][k] & 0x0f0f0f0fu; hi[r][k] = (cq[u][r][k] >> 4) & 0x0f0f0f0fu;
-                    if (Q5) { lo[r][k] |= spread((ch[u][r] >> (8 * hf + 4 * k)) & 0xfu); hi[r][k] |= spread((ch[u][r] >> (16 + 8 * hf + 4 * k)) & 0xfu); }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < NCOLS; ++c) {
-                const char * im = mmv_lds + c * img;
-                const u32x2 a0 = *(const u32x2 *) (im + ibc * 32 + 8 * hf);
-                const u32x2 a1 = *(const u32x2 *) (im + ibc * 32 + 16 + 8 * hf);
-                const float yd = *(const float *) (im + K + ibc * 4);
-                const int ysum = dot4(0x01010101u, a0[0], dot4(0x01010101u, a0[1], dot4(0x01010101u, a1[0], dot4(0x01010101u, a1[1], 0))));
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                    const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                    const int isum = dot4(lo[r][0], a0[0], dot4(lo[r][1], a0[1], dot4(hi[r][0], a1[0], dot4(hi[r][1], a1[1], 0)))) - OFF * ysum;
-                    const float t = (float) isum * (dx[r] * yd);
-                    acc[r][c] += rv ? t : 0.0f;
-                }
-            }
-        }
-        if (cit == nit - 1) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int row = cgrp * ROWS + r;
-#pragma unroll
-                for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum(acc[r][c]);
-                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
-                    acc[r][c] = 0.0f;
-                }
-            }
-        }
-        if (!more) break;
+    struct regs : qh_word<Q5> { u32x2 q; uint32_t dw; };
+    struct row  { nib_quants n; float dx; };
+    struct col  { nib_act y; int ysum; };
+    static __device__ __forceinline__ regs load(const char * bp, int hf) {
+        regs x;
+        x.dw = *(const uint16_t *) bp;
+        x.q  = *(const u32x2a2 *) (bp + QOFF + 8 * hf);
+        if constexpr (Q5) x.qh = *(const u32a2 *) (bp + 2);
+        return x;
     }
-}
+    static __device__ __forceinline__ row decode(const regs & x, int hf) {
+        uint32_t qh = 0;
+        if constexpr (Q5) qh = x.qh;
+        return { nib_unpack<Q5>(x.q, qh, hf), h2f((uint16_t) x.dw) };
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int hf, int K, int) {
+        col c;
+        c.y    = nib_read(im, ib, hf, K);
+        c.ysum = dot4(0x01010101u, c.y.a0[0], dot4(0x01010101u, c.y.a0[1], dot4(0x01010101u, c.y.a1[0], dot4(0x01010101u, c.y.a1[1], 0))));
+        return c;
+    }
+    static __device__ __forceinline__ float term(const row & w, const col & c, int) {
+        const int isum = nib_dot(w.n, c.y) - OFF * c.ysum;
+        return (float) isum * (w.dx * c.y.yd);
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum(v); }
+};
 
 // =================================================================================================
 // IQ4_NL / IQ4_XS: 4-bit indices into the 16-entry int8 table kvalues_iq4nl (ggml-common.h:1088-1090), no min term.
@@ -256,321 +255,133 @@ static __device__ __forceinline__ uint32_t iq4nl_lut4(uint32_t n) {      // n: f
     return (hi & m) | (lo & ~m);
 }
 
-// IQ4_NL: 18-B block {f16 d, qs[16]} (2-byte aligned).  Two lanes per block as k_mmv_q40: lane half hf owns qs bytes 8hf .. 8hf+7 = weights
-// 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high); 32 blocks per wave step, U steps per stage, next stage requested before the current
-// one is consumed.
-template <int NCOLS, int ROWS>
-__global__ void __launch_bounds__(256) k_mmv_iq4nl(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                  char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+// IQ4_NL: 18-B block {f16 d, qs[16]} (2-byte aligned).  Two lanes per block as Q4_0: lane half hf owns qs bytes 8hf .. 8hf+7 = weights
+// 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high); 32 blocks per wave step, U steps per stage.
+struct iq4nl_form {
+    static constexpr int LANES = 2, BYTES = 18, LOG2W = 5, ID = MMV_FORM_IQ4_NL;
+    static constexpr int U(int ncols) { return ncols <= 2 ? 2 : 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q80_image_bytes(K); }
     typedef u32x2 __attribute__((aligned(2))) u32x2a2;
-    constexpr int U = NCOLS <= 2 ? 2 : 1;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 1, hf = lane & 1;
-    const int nb  = K >> 5;
-    const int nit = (nb + 32 * U - 1) / (32 * U);
-    const size_t img = q80_image_bytes(K);
-    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * 4;
-    const int ngrp   = (nrows + ROWS - 1) / ROWS;
-
-    u32x2 q[U][ROWS]; uint32_t dw[U][ROWS];
-    auto issue = [&](int grp, int it) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int ib = (it * U + u) * 32 + g; ib = ib < nb ? ib : nb - 1;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-                const char * bp = W + (size_t) row * w_rs + (size_t) ib * 18;
-                dw[u][r] = *(const uint16_t *) bp;
-                q[u][r]  = *(const u32x2a2 *) (bp + 2 + 8 * hf);
-            }
-        }
-    };
-    int grp = wave, it = 0;
-    if (grp < ngrp) issue(grp, 0);
-    stage_act(act, act_cs, NCOLS, img);
-    __syncthreads();
-    if (grp >= ngrp) return;
-
-    float acc[ROWS][NCOLS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
-    while (true) {
-        u32x2 cq[U][ROWS]; uint32_t cd[U][ROWS];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) { cq[u][r] = q[u][r]; cd[u][r] = dw[u][r]; }
-        const int cgrp = grp, cit = it;
-        ++it;
-        if (it == nit) { it = 0; grp += nwaves; }
-        const bool more = grp < ngrp;
-        if (more) issue(grp, it);
-
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int  ib    = (cit * U + u) * 32 + g;
-            const bool valid = ib < nb;
-            const int  ibc   = valid ? ib : nb - 1;
-            uint32_t lo[ROWS][2], hi[ROWS][2]; float dx[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                dx[r] = h2f((uint16_t) cd[u][r]);
-#pragma unroll
-                for (int k = 0; k < 2; ++k) { lo[r][k] = iq4nl_lut4(cq[u][r][k] & 0x0f0f0f0fu); hi[r][k] = iq4nl_lut4((cq[u][r][k] >> 4) & 0x0f0f0f0fu); }
-            }
-#pragma unroll
-            for (int c = 0; c < NCOLS; ++c) {
-                const char * im = mmv_lds + c * img;
-                const u32x2 a0 = *(const u32x2 *) (im + ibc * 32 + 8 * hf);
-                const u32x2 a1 = *(const u32x2 *) (im + ibc * 32 + 16 + 8 * hf);
-                const float yd = *(const float *) (im + K + ibc * 4);
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                    const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                    const int isum = dot4(lo[r][0], a0[0], dot4(lo[r][1], a0[1], dot4(hi[r][0], a1[0], dot4(hi[r][1], a1[1], 0))));
-                    const float t = (float) isum * (dx[r] * yd);
-                    acc[r][c] += rv ? t : 0.0f;
-                }
-            }
-        }
-        if (cit == nit - 1) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int row = cgrp * ROWS + r;
-#pragma unroll
-                for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum(acc[r][c]);
-                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
-                    acc[r][c] = 0.0f;
-                }
-            }
-        }
-        if (!more) break;
+    struct regs { u32x2 q; uint32_t dw; };
+    struct row  { nib_quants n; float dx; };
+    typedef nib_act col;
+    static __device__ __forceinline__ regs load(const char * bp, int hf) {
+        regs x;
+        x.dw = *(const uint16_t *) bp;
+        x.q  = *(const u32x2a2 *) (bp + 2 + 8 * hf);
+        return x;
     }
-}
+    static __device__ __forceinline__ row decode(const regs & x, int) {
+        row w;
+        w.dx = h2f((uint16_t) x.dw);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) { w.n.lo[k] = iq4nl_lut4(x.q[k] & 0x0f0f0f0fu); w.n.hi[k] = iq4nl_lut4((x.q[k] >> 4) & 0x0f0f0f0fu); }
+        return w;
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int hf, int K, int) { return nib_read(im, ib, hf, K); }
+    static __device__ __forceinline__ float term(const row & w, const col & y, int) { return (float) nib_dot(w.n, y) * (w.dx * y.yd); }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum(v); }
+};
 
-// IQ4_XS: 136-B super-block {f16 d, u16 scales_h, u8 scales_l[4], qs[128]} (2-byte aligned rows), Q8_K image (mmv_lds: qs[K] | bsums | d[K/256]).
+// IQ4_XS: 136-B super-block {f16 d, u16 scales_h, u8 scales_l[4], qs[128]} (2-byte aligned rows), Q8_K image (qs[K] | bsums | d[K/256]).
 // Four lanes per super-block: lane quarter qq owns the 32-weight sub-blocks 2qq and 2qq+1 (qs bytes 32qq .. 32qq+31, two 16-byte loads) and
 // reads the 8-byte header beside them; 16 super-blocks per wave step (K = 4096: one step per row), the next row group's loads issued before
 // the current one is consumed.  ls = scales_l nibble | two bits of scales_h << 4 (dequantize_row_iq4_xs, ggml-quants.c:2530-2550).
-template <int NCOLS, int ROWS>
-__global__ void __launch_bounds__(256) k_mmv_iq4xs(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                  char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+struct iq4xs_form {
+    static constexpr int LANES = 4, BYTES = 136, LOG2W = 8, ID = MMV_FORM_IQ4_XS;
+    static constexpr int U(int) { return 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q8k_image_bytes(K); }
     typedef u32x2 __attribute__((aligned(2))) u32x2a2;
     typedef u32x4 __attribute__((aligned(2))) u32x4a2;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 2, qq = lane & 3;
-    const int nb  = K >> 8;
-    const int nit = (nb + 15) / 16;
-    const size_t img = q8k_image_bytes(K);
-    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * 4;
-    const int ngrp   = (nrows + ROWS - 1) / ROWS;
-
-    u32x2 h[ROWS]; u32x4 q[ROWS][2];
-    auto issue = [&](int grp, int it) {
-        int ib = it * 16 + g; ib = ib < nb ? ib : nb - 1;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-            const char * bp = W + (size_t) row * w_rs + (size_t) ib * 136;
-            h[r]    = *(const u32x2a2 *) bp;
-            q[r][0] = *(const u32x4a2 *) (bp + 8 + 32 * qq);
-            q[r][1] = *(const u32x4a2 *) (bp + 24 + 32 * qq);
-        }
-    };
-    int grp = wave, it = 0;
-    if (grp < ngrp) issue(grp, 0);
-    stage_act(act, act_cs, NCOLS, img);
-    __syncthreads();
-    if (grp >= ngrp) return;
-
-    float acc[ROWS][NCOLS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
-    while (true) {
-        u32x2 ch[ROWS]; u32x4 cq[ROWS][2];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) { ch[r] = h[r]; cq[r][0] = q[r][0]; cq[r][1] = q[r][1]; }
-        const int cgrp = grp, cit = it;
-        ++it;
-        if (it == nit) { it = 0; grp += nwaves; }
-        const bool more = grp < ngrp;
-        if (more) issue(grp, it);
-
-        const int  ib    = cit * 16 + g;
-        const bool valid = ib < nb;
-        const int  ibc   = valid ? ib : nb - 1;
-        uint32_t lo[ROWS][2][4], hi[ROWS][2][4]; int ls[ROWS][2]; float dx[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            dx[r] = h2f((uint16_t) (ch[r][0] & 0xffffu));
-            const uint32_t sh = (ch[r][0] >> 16) >> (4 * qq), sl = (ch[r][1] >> (8 * qq)) & 0xffu;
-            ls[r][0] = (int) ((sl & 0xfu) | ((sh & 3u) << 4)) - 32;
-            ls[r][1] = (int) ((sl >> 4) | (((sh >> 2) & 3u) << 4)) - 32;
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { lo[r][sb][k] = iq4nl_lut4(cq[r][sb][k] & 0x0f0f0f0fu); hi[r][sb][k] = iq4nl_lut4((cq[r][sb][k] >> 4) & 0x0f0f0f0fu); }
-        }
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) {
-            const char * im = mmv_lds + c * img + (size_t) ibc * 256 + 64 * qq;
-            u32x4 a[2][2];
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb) { a[sb][0] = *(const u32x4 *) (im + 32 * sb); a[sb][1] = *(const u32x4 *) (im + 32 * sb + 16); }
-            const float yd = *(const float *) (mmv_lds + c * img + K + K / 8 + ibc * 4);
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                int isum = 0;
-#pragma unroll
-                for (int sb = 0; sb < 2; ++sb) {
-                    int s = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) s = dot4(lo[r][sb][k], a[sb][0][k], dot4(hi[r][sb][k], a[sb][1][k], s));
-                    isum += ls[r][sb] * s;
-                }
-                const float t = (float) isum * (dx[r] * yd);
-                acc[r][c] += rv ? t : 0.0f;
-            }
-        }
-        if (cit == nit - 1) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int row = cgrp * ROWS + r;
-#pragma unroll
-                for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum(acc[r][c]);
-                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
-                    acc[r][c] = 0.0f;
-                }
-            }
-        }
-        if (!more) break;
+    struct regs { u32x2 h; u32x4 q[2]; };
+    struct row  { uint32_t lo[2][4], hi[2][4]; int ls[2]; float dx; };
+    struct col  { u32x4 a[2][2]; float yd; };
+    static __device__ __forceinline__ regs load(const char * bp, int qq) {
+        regs x;
+        x.h    = *(const u32x2a2 *) bp;
+        x.q[0] = *(const u32x4a2 *) (bp + 8 + 32 * qq);
+        x.q[1] = *(const u32x4a2 *) (bp + 24 + 32 * qq);
+        return x;
     }
-}
+    static __device__ __forceinline__ row decode(const regs & x, int qq) {
+        row w;
+        w.dx = h2f((uint16_t) (x.h[0] & 0xffffu));
+        const uint32_t sh = (x.h[0] >> 16) >> (4 * qq), sl = (x.h[1] >> (8 * qq)) & 0xffu;
+        w.ls[0] = (int) ((sl & 0xfu) | ((sh & 3u) << 4)) - 32;
+        w.ls[1] = (int) ((sl >> 4) | (((sh >> 2) & 3u) << 4)) - 32;
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { w.lo[sb][k] = iq4nl_lut4(x.q[sb][k] & 0x0f0f0f0fu); w.hi[sb][k] = iq4nl_lut4((x.q[sb][k] >> 4) & 0x0f0f0f0fu); }
+        return w;
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int qq, int K, int) {
+        col y;
+        const char * p = im + (size_t) ib * 256 + 64 * qq;
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb) { y.a[sb][0] = *(const u32x4 *) (p + 32 * sb); y.a[sb][1] = *(const u32x4 *) (p + 32 * sb + 16); }
+        y.yd = *(const float *) (im + K + K / 8 + ib * 4);
+        return y;
+    }
+    static __device__ __forceinline__ float term(const row & w, const col & y, int) {
+        int isum = 0;
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb) {
+            int s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s = dot4(w.lo[sb][k], y.a[sb][0][k], dot4(w.hi[sb][k], y.a[sb][1][k], s));
+            isum += w.ls[sb] * s;
+        }
+        return (float) isum * (w.dx * y.yd);
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum(v); }
+};
 
 // =================================================================================================
 // Q4_1 / Q5_1 weights x Q8_1 activations.  reference: ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1 (ggml-cpu/arch/x86/quants.c:701-758, :925):
 //   sumi = sum_j (x.qs[j] & 0xF [| fifth bit]) * y.qs[j] + (x.qs[j] >> 4 [| fifth bit]) * y.qs[j + 16]      (quants unsigned: 0..15 / 0..31)
-//   sumf += (d_x * d_y) * sumi + m_x * s_y,      s_y = f16(d_y * sum(y.qs)) from the Q8_1 image (mmv_lds: qs[K] | d[K/32] | s[K/32])
+//   sumf += (d_x * d_y) * sumi + m_x * s_y,      s_y = f16(d_y * sum(y.qs)) from the Q8_1 image (qs[K] | d[K/32] | s[K/32])
 // Blocks are 20 B {f16 d, f16 m, qs[16]} / 24 B {f16 d, f16 m, u32 qh, qs[16]}: rows and blocks are 4-byte aligned only, so every load is
-// a dword or a dword pair.  Two lanes per block as k_mmv_q40: lane half hf owns qs bytes 8hf .. 8hf+7 = weights 8hf..8hf+7 (low nibbles)
+// a dword or a dword pair.  Two lanes per block as Q4_0: lane half hf owns qs bytes 8hf .. 8hf+7 = weights 8hf..8hf+7 (low nibbles)
 // and 16+8hf..23+8hf (high) and reads the header dword(s) beside them; half 0 adds the block's m_x * s_y.  32 blocks per wave step, U steps
-// per stage, the next stage requested before the current one is consumed.
+// per stage.
 // =================================================================================================
-template <int NCOLS, int ROWS, bool Q5>
-__global__ void __launch_bounds__(256) k_mmv_q41(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+template <bool Q5>
+struct q41_form {
+    static constexpr int LANES = 2, BYTES = Q5 ? 24 : 20, LOG2W = 5, ID = Q5 ? MMV_FORM_Q5_1 : MMV_FORM_Q4_1;
+    static constexpr int QOFF = Q5 ? 8 : 4;
+    static constexpr int U(int ncols) { return ncols <= 2 ? 2 : 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q81_image_bytes(K); }
     typedef u32x2 __attribute__((aligned(4))) u32x2a4;
-    constexpr int BS = Q5 ? 24 : 20, QOFF = Q5 ? 8 : 4;
-    constexpr int U = NCOLS <= 2 ? 2 : 1;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 1, hf = lane & 1;
-    const int nb  = K >> 5;
-    const int nit = (nb + 32 * U - 1) / (32 * U);
-    const size_t img = q81_image_bytes(K);
-    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * 4;
-    const int ngrp   = (nrows + ROWS - 1) / ROWS;
-
-    u32x2 q[U][ROWS]; uint32_t dm[U][ROWS], qh[Q5 ? U : 1][Q5 ? ROWS : 1];
-    auto issue = [&](int grp, int it) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            int ib = (it * U + u) * 32 + g; ib = ib < nb ? ib : nb - 1;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-                const char * bp = W + (size_t) row * w_rs + (size_t) ib * BS;
-                dm[u][r] = *(const uint32_t *) bp;
-                q[u][r]  = *(const u32x2a4 *) (bp + QOFF + 8 * hf);
-                if (Q5) qh[u][r] = *(const uint32_t *) (bp + 4);
-            }
-        }
-    };
-    // fifth bits of 4 consecutive weights (bits b .. b+3 of qh) spread into bit 4 of the four bytes of a word
-    auto spread = [](uint32_t bits) { return ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) << 4; };
-    int grp = wave, it = 0;
-    if (grp < ngrp) issue(grp, 0);
-    stage_act(act, act_cs, NCOLS, img);
-    __syncthreads();
-    if (grp >= ngrp) return;
-
-    float acc[ROWS][NCOLS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
-    while (true) {
-        u32x2 cq[U][ROWS]; uint32_t cd[U][ROWS], ch[Q5 ? U : 1][Q5 ? ROWS : 1];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) { cq[u][r] = q[u][r]; cd[u][r] = dm[u][r]; if (Q5) ch[u][r] = qh[u][r]; }
-        const int cgrp = grp, cit = it;
-        ++it;
-        if (it == nit) { it = 0; grp += nwaves; }
-        const bool more = grp < ngrp;
-        if (more) issue(grp, it);
-
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int  ib    = (cit * U + u) * 32 + g;
-            const bool valid = ib < nb;
-            const int  ibc   = valid ? ib : nb - 1;
-            uint32_t lo[ROWS][2], hi[ROWS][2]; float dx[ROWS], mx[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                dx[r] = h2f((uint16_t) (cd[u][r] & 0xffffu));
-                mx[r] = hf == 0 ? h2f((uint16_t) (cd[u][r] >> 16)) : 0.0f;
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    lo[r][k] = cq[u][r][k] & 0x0f0f0f0fu; hi[r][k] = (cq[u][r][k] >> 4) & 0x0f0f0f0fu;
-                    if (Q5) { lo[r][k] |= spread((ch[u][r] >> (8 * hf + 4 * k)) & 0xfu); hi[r][k] |= spread((ch[u][r] >> (16 + 8 * hf + 4 * k)) & 0xfu); }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < NCOLS; ++c) {
-                const char * im = mmv_lds + c * img;
-                const u32x2 a0 = *(const u32x2 *) (im + ibc * 32 + 8 * hf);
-                const u32x2 a1 = *(const u32x2 *) (im + ibc * 32 + 16 + 8 * hf);
-                const float yd = *(const float *) (im + K + ibc * 4);
-                const float ys = *(const float *) (im + K + (nb + ibc) * 4);
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                    const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                    const int isum = dot4(lo[r][0], a0[0], dot4(lo[r][1], a0[1], dot4(hi[r][0], a1[0], dot4(hi[r][1], a1[1], 0))));
-                    const float t = (float) isum * (dx[r] * yd) + (hf == 0 ? mx[r] * ys : 0.0f);
-                    acc[r][c] += rv ? t : 0.0f;
-                }
-            }
-        }
-        if (cit == nit - 1) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int row = cgrp * ROWS + r;
-#pragma unroll
-                for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum_f32(acc[r][c]);
-                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
-                    acc[r][c] = 0.0f;
-                }
-            }
-        }
-        if (!more) break;
+    struct regs : qh_word<Q5> { u32x2 q; uint32_t dm; };
+    struct row  { nib_quants n; float dx, mx; };
+    struct col  { nib_act y; float ys; };
+    static __device__ __forceinline__ regs load(const char * bp, int hf) {
+        regs x;
+        x.dm = *(const uint32_t *) bp;
+        x.q  = *(const u32x2a4 *) (bp + QOFF + 8 * hf);
+        if constexpr (Q5) x.qh = *(const uint32_t *) (bp + 4);
+        return x;
     }
-}
+    static __device__ __forceinline__ row decode(const regs & x, int hf) {
+        uint32_t qh = 0;
+        if constexpr (Q5) qh = x.qh;
+        return { nib_unpack<Q5>(x.q, qh, hf), h2f((uint16_t) (x.dm & 0xffffu)), hf == 0 ? h2f((uint16_t) (x.dm >> 16)) : 0.0f };
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int hf, int K, int nb) {
+        col c;
+        c.y  = nib_read(im, ib, hf, K);
+        c.ys = *(const float *) (im + K + (nb + ib) * 4);
+        return c;
+    }
+    static __device__ __forceinline__ float term(const row & w, const col & c, int hf) {
+        return (float) nib_dot(w.n, c.y) * (w.dx * c.y.yd) + (hf == 0 ? w.mx * c.ys : 0.0f);
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum_f32(v); }
+};
 
 // =================================================================================================
-// Q2_K / Q3_K weights x Q8_K activations (mmv_lds: qs[K] | bsums[K/16] int16 | d[K/256]).  Both formats cut a 256-weight super-block into sixteen
+// Q2_K / Q3_K weights x Q8_K activations (image: qs[K] | bsums[K/16] int16 | d[K/256]).  Both formats cut a 256-weight super-block into sixteen
 // 16-weight groups: group k = 8n + 2j + sub covers weights 128n + 32j + 16sub .. +15, whose 2-bit quants are bits 2j, 2j+1 of qs bytes
 // 32n + 16sub .. +15 (dequantize_row_q2_K / _q3_K, ggml-quants.c:784 / :1128) -- bsums[k] of the image is the sum of exactly those activations.
 // Four lanes per super-block: lane quarter qq = 2n + sub owns those 16 qs bytes (one 16-byte load), i.e. the four groups j = 0..3 of its (n, sub);
@@ -581,223 +392,116 @@ __global__ void __launch_bounds__(256) k_mmv_q41(const char * __restrict__ W, si
 //                 sumf += (d_y * d_x) * sum_k (sc_k - 32) * sum(q3 * q8),   q3 = 2 low bits | hmask bit << 2, minus 4  (the 4 taken out: - 4 * bsums[k])
 // All sums are exact integers; the four lanes of a super-block each convert their quarter, which the reference converts in eight SIMD lanes.
 // =================================================================================================
+struct k16_act { u32x4 a[4]; int bsum[4]; float yd; };           // the activations of the lane's four groups, their sums, the super-block's scale
+static __device__ __forceinline__ k16_act k16_read(const char * im, int ib, int qq, int K) {
+    const int n = qq >> 1, sub = qq & 1;
+    k16_act y;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y.a[j] = *(const u32x4 *) (im + (size_t) ib * 256 + 128 * n + 32 * j + 16 * sub);
+    const u32x4 bs = *(const u32x4 *) (im + K + ib * 32 + 16 * n);          // bsums[8n .. 8n+7]: group j of this lane is element 2j + sub
+    y.yd = *(const float *) (im + K + K / 8 + ib * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y.bsum[j] = ((int) (bs[j] << (16 - 16 * sub))) >> 16;
+    return y;
+}
+
 // Q2_K: 84-B block {scales[16], qs[64], f16 d, f16 dmin}, 4-byte aligned: the lane reads its 16 qs bytes, the 8 scale bytes of its half n
 // (its own four are bytes 2j + sub of them) and the d / dmin dword.
-template <int NCOLS, int ROWS>
-__global__ void __launch_bounds__(256) k_mmv_q2k(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+struct q2k_form {
+    static constexpr int LANES = 4, BYTES = 84, LOG2W = 8, ID = MMV_FORM_Q2_K;
+    static constexpr int U(int) { return 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q8k_image_bytes(K); }
     typedef u32x2 __attribute__((aligned(4))) u32x2a4;
     typedef u32x4 __attribute__((aligned(4))) u32x4a4;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 2, qq = lane & 3, n = qq >> 1, sub = qq & 1;
-    const int nb  = K >> 8;
-    const int nit = (nb + 15) / 16;
-    const size_t img = q8k_image_bytes(K);
-    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * 4;
-    const int ngrp   = (nrows + ROWS - 1) / ROWS;
-
-    u32x4 q[ROWS]; u32x2 sc[ROWS]; uint32_t dd[ROWS];
-    auto issue = [&](int grp, int it) {
-        int ib = it * 16 + g; ib = ib < nb ? ib : nb - 1;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-            const char * bp = W + (size_t) row * w_rs + (size_t) ib * 84;
-            sc[r] = *(const u32x2a4 *) (bp + 8 * n);
-            q[r]  = *(const u32x4a4 *) (bp + 16 + 16 * qq);
-            dd[r] = *(const uint32_t *) (bp + 80);
-        }
-    };
-    int grp = wave, it = 0;
-    if (grp < ngrp) issue(grp, 0);
-    stage_act(act, act_cs, NCOLS, img);
-    __syncthreads();
-    if (grp >= ngrp) return;
-
-    float acc[ROWS][NCOLS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
-    while (true) {
-        u32x4 cq[ROWS]; u32x2 cs[ROWS]; uint32_t cd[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) { cq[r] = q[r]; cs[r] = sc[r]; cd[r] = dd[r]; }
-        const int cgrp = grp, cit = it;
-        ++it;
-        if (it == nit) { it = 0; grp += nwaves; }
-        const bool more = grp < ngrp;
-        if (more) issue(grp, it);
-
-        const int  ib    = cit * 16 + g;
-        const bool valid = ib < nb;
-        const int  ibc   = valid ? ib : nb - 1;
-        uint32_t q2[ROWS][4][4]; int scl[ROWS][4], mn[ROWS][4]; float dx[ROWS], dmin[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            dx[r] = h2f((uint16_t) (cd[r] & 0xffffu)); dmin[r] = h2f((uint16_t) (cd[r] >> 16));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t sb = (cs[r][j >> 1] >> (8 * (2 * (j & 1) + sub))) & 0xffu;
-                scl[r][j] = (int) (sb & 0xfu); mn[r][j] = (int) (sb >> 4);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) q2[r][j][k] = (cq[r][k] >> (2 * j)) & 0x03030303u;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) {
-            const char * im = mmv_lds + c * img;
-            u32x4 a[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = *(const u32x4 *) (im + (size_t) ibc * 256 + 128 * n + 32 * j + 16 * sub);
-            const u32x4 bs = *(const u32x4 *) (im + K + ibc * 32 + 16 * n);          // bsums[8n .. 8n+7]: group j of this lane is element 2j + sub
-            const float yd = *(const float *) (im + K + K / 8 + ibc * 4);
-            int bsum[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bsum[j] = ((int) (bs[j] << (16 - 16 * sub))) >> 16;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                int isum = 0, msum = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int s = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) s = dot4(q2[r][j][k], a[j][k], s);
-                    isum += scl[r][j] * s;
-                    msum += mn[r][j] * bsum[j];
-                }
-                const float t = (yd * dx[r]) * (float) isum - (yd * dmin[r]) * (float) msum;
-                acc[r][c] += rv ? t : 0.0f;
-            }
-        }
-        if (cit == nit - 1) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int row = cgrp * ROWS + r;
-#pragma unroll
-                for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum_f32(acc[r][c]);
-                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
-                    acc[r][c] = 0.0f;
-                }
-            }
-        }
-        if (!more) break;
+    struct regs { u32x4 q; u32x2 sc; uint32_t dd; };
+    struct row  { uint32_t q2[4][4]; int scl[4], mn[4]; float dx, dmin; };
+    typedef k16_act col;
+    static __device__ __forceinline__ regs load(const char * bp, int qq) {
+        regs x;
+        x.sc = *(const u32x2a4 *) (bp + 8 * (qq >> 1));
+        x.q  = *(const u32x4a4 *) (bp + 16 + 16 * qq);
+        x.dd = *(const uint32_t *) (bp + 80);
+        return x;
     }
-}
+    static __device__ __forceinline__ row decode(const regs & x, int qq) {
+        const int sub = qq & 1;
+        row w;
+        w.dx = h2f((uint16_t) (x.dd & 0xffffu)); w.dmin = h2f((uint16_t) (x.dd >> 16));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t sb = (x.sc[j >> 1] >> (8 * (2 * (j & 1) + sub))) & 0xffu;
+            w.scl[j] = (int) (sb & 0xfu); w.mn[j] = (int) (sb >> 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w.q2[j][k] = (x.q[k] >> (2 * j)) & 0x03030303u;
+        }
+        return w;
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int qq, int K, int) { return k16_read(im, ib, qq, K); }
+    static __device__ __forceinline__ float term(const row & w, const col & y, int) {
+        int isum = 0, msum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s = dot4(w.q2[j][k], y.a[j][k], s);
+            isum += w.scl[j] * s;
+            msum += w.mn[j] * y.bsum[j];
+        }
+        return (y.yd * w.dx) * (float) isum - (y.yd * w.dmin) * (float) msum;
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum_f32(v); }
+};
 
 // Q3_K: 110-B block {hmask[32], qs[64], scales[12], f16 d}, 2-byte aligned only (110 = 2 * 55): no field of a block has a fixed dword phase, so
 // the lane mapping is built on three 16-byte loads that the hardware takes at any 2-byte address and that all stay inside the block --
 //   hmask bytes 16sub .. +15 (bit 4n + j of byte l is the high bit of group j's weight l), qs bytes 16qq .. +15, and bytes 94 .. 109:
 //   the last two qs bytes (unused), the 12 scale bytes and d -- a 16-byte load at 96 would run two bytes past the tensor's last block.
 // The 6-bit scales are unpacked as the reference does (kmask1 / kmask2 on three dwords): scale k is byte k & 3 of word k >> 2.
-template <int NCOLS, int ROWS>
-__global__ void __launch_bounds__(256) k_mmv_q3k(const char * __restrict__ W, size_t w_rs, const char * __restrict__ act, size_t act_cs,
-                                                char * __restrict__ dst, size_t dst_cs, int K, int nrows) {
+struct q3k_form {
+    static constexpr int LANES = 4, BYTES = 110, LOG2W = 8, ID = MMV_FORM_Q3_K;
+    static constexpr int U(int) { return 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q8k_image_bytes(K); }
     typedef u32x4 __attribute__((aligned(2))) u32x4a2;
-    const int lane = threadIdx.x & 63;
-    const int g = lane >> 2, qq = lane & 3, n = qq >> 1, sub = qq & 1;
-    const int nb  = K >> 8;
-    const int nit = (nb + 15) / 16;
-    const size_t img = q8k_image_bytes(K);
-    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int nwaves = gridDim.x * 4;
-    const int ngrp   = (nrows + ROWS - 1) / ROWS;
-
-    u32x4 hm[ROWS], q[ROWS], hd[ROWS];
-    auto issue = [&](int grp, int it) {
-        int ib = it * 16 + g; ib = ib < nb ? ib : nb - 1;
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
-            const char * bp = W + (size_t) row * w_rs + (size_t) ib * 110;
-            hm[r] = *(const u32x4a2 *) (bp + 16 * sub);
-            q[r]  = *(const u32x4a2 *) (bp + 32 + 16 * qq);
-            hd[r] = *(const u32x4a2 *) (bp + 94);
-        }
-    };
-    int grp = wave, it = 0;
-    if (grp < ngrp) issue(grp, 0);
-    stage_act(act, act_cs, NCOLS, img);
-    __syncthreads();
-    if (grp >= ngrp) return;
-
-    float acc[ROWS][NCOLS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) acc[r][c] = 0.0f;
-    while (true) {
-        u32x4 chm[ROWS], cq[ROWS], chd[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) { chm[r] = hm[r]; cq[r] = q[r]; chd[r] = hd[r]; }
-        const int cgrp = grp, cit = it;
-        ++it;
-        if (it == nit) { it = 0; grp += nwaves; }
-        const bool more = grp < ngrp;
-        if (more) issue(grp, it);
-
-        const int  ib    = cit * 16 + g;
-        const bool valid = ib < nb;
-        const int  ibc   = valid ? ib : nb - 1;
-        uint32_t q3[ROWS][4][4]; int scl[ROWS][4]; float dx[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            const uint32_t aux0 = (chd[r][0] >> 16) | (chd[r][1] << 16), aux1 = (chd[r][1] >> 16) | (chd[r][2] << 16), aux2 = (chd[r][2] >> 16) | (chd[r][3] << 16);
-            dx[r] = h2f((uint16_t) (chd[r][3] >> 16));
-            // words 2n and 2n + 1 of the reference's scales128: scales 8n .. 8n+3 and 8n+4 .. 8n+7
-            const uint32_t sa = ((aux0 >> (4 * n)) & 0x0f0f0f0fu) | (((aux2 >> (4 * n)) & 0x03030303u) << 4);
-            const uint32_t sb = ((aux1 >> (4 * n)) & 0x0f0f0f0fu) | (((aux2 >> (4 * n + 2)) & 0x03030303u) << 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                scl[r][j] = (int) (((j < 2 ? sa : sb) >> (8 * (2 * (j & 1) + sub))) & 0xffu) - 32;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) q3[r][j][k] = ((cq[r][k] >> (2 * j)) & 0x03030303u) | (((chm[r][k] >> (4 * n + j)) & 0x01010101u) << 2);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NCOLS; ++c) {
-            const char * im = mmv_lds + c * img;
-            u32x4 a[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = *(const u32x4 *) (im + (size_t) ibc * 256 + 128 * n + 32 * j + 16 * sub);
-            const u32x4 bs = *(const u32x4 *) (im + K + ibc * 32 + 16 * n);          // bsums[8n .. 8n+7]: group j of this lane is element 2j + sub
-            const float yd = *(const float *) (im + K + K / 8 + ibc * 4);
-            int bsum[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bsum[j] = ((int) (bs[j] << (16 - 16 * sub))) >> 16;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const bool rv = valid && (cgrp * ROWS + r) < nrows;
-                int isum = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int s = -4 * bsum[j];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) s = dot4(q3[r][j][k], a[j][k], s);
-                    isum += scl[r][j] * s;
-                }
-                const float t = (yd * dx[r]) * (float) isum;
-                acc[r][c] += rv ? t : 0.0f;
-            }
-        }
-        if (cit == nit - 1) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const int row = cgrp * ROWS + r;
-#pragma unroll
-                for (int c = 0; c < NCOLS; ++c) {
-                    const float s = wave_sum_f32(acc[r][c]);
-                    if (lane == 0 && row < nrows) *(float *) (dst + c * dst_cs + (size_t) row * 4) = s;
-                    acc[r][c] = 0.0f;
-                }
-            }
-        }
-        if (!more) break;
+    struct regs { u32x4 hm, q, hd; };
+    struct row  { uint32_t q3[4][4]; int scl[4]; float dx; };
+    typedef k16_act col;
+    static __device__ __forceinline__ regs load(const char * bp, int qq) {
+        regs x;
+        x.hm = *(const u32x4a2 *) (bp + 16 * (qq & 1));
+        x.q  = *(const u32x4a2 *) (bp + 32 + 16 * qq);
+        x.hd = *(const u32x4a2 *) (bp + 94);
+        return x;
     }
-}
+    static __device__ __forceinline__ row decode(const regs & x, int qq) {
+        const int n = qq >> 1, sub = qq & 1;
+        row w;
+        const uint32_t aux0 = (x.hd[0] >> 16) | (x.hd[1] << 16), aux1 = (x.hd[1] >> 16) | (x.hd[2] << 16), aux2 = (x.hd[2] >> 16) | (x.hd[3] << 16);
+        w.dx = h2f((uint16_t) (x.hd[3] >> 16));
+        // words 2n and 2n + 1 of the reference's scales128: scales 8n .. 8n+3 and 8n+4 .. 8n+7
+        const uint32_t sa = ((aux0 >> (4 * n)) & 0x0f0f0f0fu) | (((aux2 >> (4 * n)) & 0x03030303u) << 4);
+        const uint32_t sb = ((aux1 >> (4 * n)) & 0x0f0f0f0fu) | (((aux2 >> (4 * n + 2)) & 0x03030303u) << 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            w.scl[j] = (int) (((j < 2 ? sa : sb) >> (8 * (2 * (j & 1) + sub))) & 0xffu) - 32;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w.q3[j][k] = ((x.q[k] >> (2 * j)) & 0x03030303u) | (((x.hm[k] >> (4 * n + j)) & 0x01010101u) << 2);
+        }
+        return w;
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int qq, int K, int) { return k16_read(im, ib, qq, K); }
+    static __device__ __forceinline__ float term(const row & w, const col & y, int) {
+        int isum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int s = -4 * y.bsum[j];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s = dot4(w.q3[j][k], y.a[j][k], s);
+            isum += w.scl[j] * s;
+        }
+        return (y.yd * w.dx) * (float) isum;
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum_f32(v); }
+};
 
 // =================================================================================================
 // F16 / F32 weights: each lane consumes 16 B (8 halfs / 4 floats) per step; activations (f16 rows for F16
@@ -1026,108 +730,39 @@ void mmv_q4_K(const mmv_args & a, hipStream_t st) { mmv_kquant_single(GGML_TYPE_
 void mmv_q6_K(const mmv_args & a, hipStream_t st) { mmv_kquant_single(GGML_TYPE_Q6_K, a, st); }
 void mmv_q5_K(const mmv_args & a, hipStream_t st) { mmv_kquant_single(GGML_TYPE_Q5_K, a, st); }
 
-void mmv_q8_0(const mmv_args & a0, hipStream_t st) {
+// the block formats: one launch per call of up to 8 columns (1 - 4 columns: two rows per wave, 5 - 8: one), counted per form
+static long g_blocks_launches[MMV_FORM_COUNT];
+long mmv_blocks_launches(int form) { return form >= 0 && form < MMV_FORM_COUNT ? g_blocks_launches[form] : 0; }
+template <class Form>
+static void mmv_blocks_launch(const mmv_args & a0, hipStream_t st) {
     if (a0.nrows == 0 || a0.ncols == 0) return;
-    const size_t ib = q80_image_bytes(a0.K);
+    const size_t ib = Form::image_bytes(a0.K);
     split_cols(a0, ib, [&](const mmv_args & a) {
         mmv_kernel_t k = nullptr; int rows = 2;
         switch (a.ncols) {
-            case 1: k = k_mmv_q80<1, 2>; break;
-            case 2: k = k_mmv_q80<2, 2>; break;
-            case 3: k = k_mmv_q80<3, 2>; break;
-            case 4: k = k_mmv_q80<4, 2>; break;
-            case 5: k = k_mmv_q80<5, 1>; rows = 1; break;
-            case 6: k = k_mmv_q80<6, 1>; rows = 1; break;
-            case 7: k = k_mmv_q80<7, 1>; rows = 1; break;
-            case 8: k = k_mmv_q80<8, 1>; rows = 1; break;
+            case 1: k = k_mmv_blocks<Form, 1, 2>; break;
+            case 2: k = k_mmv_blocks<Form, 2, 2>; break;
+            case 3: k = k_mmv_blocks<Form, 3, 2>; break;
+            case 4: k = k_mmv_blocks<Form, 4, 2>; break;
+            case 5: k = k_mmv_blocks<Form, 5, 1>; rows = 1; break;
+            case 6: k = k_mmv_blocks<Form, 6, 1>; rows = 1; break;
+            case 7: k = k_mmv_blocks<Form, 7, 1>; rows = 1; break;
+            case 8: k = k_mmv_blocks<Form, 8, 1>; rows = 1; break;
             default: abort();
         }
         launch_mmv(k, rows, ib * a.ncols, a, st);
+        ++g_blocks_launches[Form::ID];
     });
 }
-
-template <bool Q5>
-static void mmv_q40_t(const mmv_args & a0, hipStream_t st) {
-    if (a0.nrows == 0 || a0.ncols == 0) return;
-    const size_t ib = q80_image_bytes(a0.K);
-    split_cols(a0, ib, [&](const mmv_args & a) {
-        mmv_kernel_t k = nullptr; int rows = 2;
-        switch (a.ncols) {
-            case 1: k = k_mmv_q40<1, 2, Q5>; break;
-            case 2: k = k_mmv_q40<2, 2, Q5>; break;
-            case 3: k = k_mmv_q40<3, 2, Q5>; break;
-            case 4: k = k_mmv_q40<4, 2, Q5>; break;
-            case 5: k = k_mmv_q40<5, 1, Q5>; rows = 1; break;
-            case 6: k = k_mmv_q40<6, 1, Q5>; rows = 1; break;
-            case 7: k = k_mmv_q40<7, 1, Q5>; rows = 1; break;
-            case 8: k = k_mmv_q40<8, 1, Q5>; rows = 1; break;
-            default: abort();
-        }
-        launch_mmv(k, rows, ib * a.ncols, a, st);
-    });
-}
-void mmv_q4_0(const mmv_args & a, hipStream_t st) { mmv_q40_t<false>(a, st); }
-void mmv_q5_0(const mmv_args & a, hipStream_t st) { mmv_q40_t<true>(a, st); }
-
-static long g_iq4_launches[2] = { 0, 0 };
-long mmv_iq4_launches(bool xs) { return g_iq4_launches[xs ? 1 : 0]; }
-template <bool XS>
-static void mmv_iq4_t(const mmv_args & a0, hipStream_t st) {
-    if (a0.nrows == 0 || a0.ncols == 0) return;
-    const size_t ib = XS ? q8k_image_bytes(a0.K) : q80_image_bytes(a0.K);
-    split_cols(a0, ib, [&](const mmv_args & a) {
-        mmv_kernel_t k = nullptr; int rows = 2;
-        switch (a.ncols) {
-            case 1: k = XS ? k_mmv_iq4xs<1, 2> : k_mmv_iq4nl<1, 2>; break;
-            case 2: k = XS ? k_mmv_iq4xs<2, 2> : k_mmv_iq4nl<2, 2>; break;
-            case 3: k = XS ? k_mmv_iq4xs<3, 2> : k_mmv_iq4nl<3, 2>; break;
-            case 4: k = XS ? k_mmv_iq4xs<4, 2> : k_mmv_iq4nl<4, 2>; break;
-            case 5: k = XS ? k_mmv_iq4xs<5, 1> : k_mmv_iq4nl<5, 1>; rows = 1; break;
-            case 6: k = XS ? k_mmv_iq4xs<6, 1> : k_mmv_iq4nl<6, 1>; rows = 1; break;
-            case 7: k = XS ? k_mmv_iq4xs<7, 1> : k_mmv_iq4nl<7, 1>; rows = 1; break;
-            case 8: k = XS ? k_mmv_iq4xs<8, 1> : k_mmv_iq4nl<8, 1>; rows = 1; break;
-            default: abort();
-        }
-        launch_mmv(k, rows, ib * a.ncols, a, st);
-        ++g_iq4_launches[XS ? 1 : 0];
-    });
-}
-void mmv_iq4_nl(const mmv_args & a, hipStream_t st) { mmv_iq4_t<false>(a, st); }
-void mmv_iq4_xs(const mmv_args & a, hipStream_t st) { mmv_iq4_t<true>(a, st); }
-
-// Q4_1 / Q5_1 (Q8_1 images) and Q2_K / Q3_K (Q8_K images): one launch per call of up to 8 columns, counted per type
-static long g_lowbit_launches[4] = { 0, 0, 0, 0 };
-long mmv_lowbit_launches(int which) { return which >= 0 && which < 4 ? g_lowbit_launches[which] : 0; }
-#define MMV_LOWBIT_PICK(KERNEL, ...)                                     \
-    switch (a.ncols) {                                                   \
-        case 1: k = KERNEL<1, 2, ##__VA_ARGS__>; break;                  \
-        case 2: k = KERNEL<2, 2, ##__VA_ARGS__>; break;                  \
-        case 3: k = KERNEL<3, 2, ##__VA_ARGS__>; break;                  \
-        case 4: k = KERNEL<4, 2, ##__VA_ARGS__>; break;                  \
-        case 5: k = KERNEL<5, 1, ##__VA_ARGS__>; rows = 1; break;        \
-        case 6: k = KERNEL<6, 1, ##__VA_ARGS__>; rows = 1; break;        \
-        case 7: k = KERNEL<7, 1, ##__VA_ARGS__>; rows = 1; break;        \
-        case 8: k = KERNEL<8, 1, ##__VA_ARGS__>; rows = 1; break;        \
-        default: abort();                                                \
-    }
-template <int WHICH>
-static void mmv_lowbit_t(const mmv_args & a0, hipStream_t st) {
-    if (a0.nrows == 0 || a0.ncols == 0) return;
-    const size_t ib = (WHICH == MMV_LOWBIT_Q41 || WHICH == MMV_LOWBIT_Q51) ? q81_image_bytes(a0.K) : q8k_image_bytes(a0.K);
-    split_cols(a0, ib, [&](const mmv_args & a) {
-        mmv_kernel_t k = nullptr; int rows = 2;
-        if      (WHICH == MMV_LOWBIT_Q41) { MMV_LOWBIT_PICK(k_mmv_q41, false) }
-        else if (WHICH == MMV_LOWBIT_Q51) { MMV_LOWBIT_PICK(k_mmv_q41, true) }
-        else if (WHICH == MMV_LOWBIT_Q2K) { MMV_LOWBIT_PICK(k_mmv_q2k) }
-        else                              { MMV_LOWBIT_PICK(k_mmv_q3k) }
-        launch_mmv(k, rows, ib * a.ncols, a, st);
-        ++g_lowbit_launches[WHICH];
-    });
-}
-void mmv_q4_1(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q41>(a, st); }
-void mmv_q5_1(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q51>(a, st); }
-void mmv_q2_K(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q2K>(a, st); }
-void mmv_q3_K(const mmv_args & a, hipStream_t st) { mmv_lowbit_t<MMV_LOWBIT_Q3K>(a, st); }
+void mmv_q8_0(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q80_form>(a, st); }
+void mmv_q4_0(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q40_form<false>>(a, st); }
+void mmv_q5_0(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q40_form<true>>(a, st); }
+void mmv_iq4_nl(const mmv_args & a, hipStream_t st) { mmv_blocks_launch<iq4nl_form>(a, st); }
+void mmv_iq4_xs(const mmv_args & a, hipStream_t st) { mmv_blocks_launch<iq4xs_form>(a, st); }
+void mmv_q4_1(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q41_form<false>>(a, st); }
+void mmv_q5_1(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q41_form<true>>(a, st); }
+void mmv_q2_K(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q2k_form>(a, st); }
+void mmv_q3_K(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q3k_form>(a, st); }
 
 #define MMVF_LAUNCH(NC, ROWS, WF16)                                                                                    \
     do {                                                                                                               \

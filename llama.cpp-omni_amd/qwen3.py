@@ -110,6 +110,13 @@ def random_blocks(rng, ty, nrows, K, std=0.02):
         blk[..., 0:2] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
         blk[..., 2:] = rng.integers(0, 256, size=(nrows, nb, 16), dtype=np.uint8)
         return blk.reshape(nrows, nb * 18)
+    if ty == 6:                                              # Q5_0: value = (q - 16) * d, q in [0, 31]: std ~ 9.2 d
+        nb = K // 32
+        blk = np.empty((nrows, nb, 22), dtype=np.uint8)
+        d = (std / 9.2) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., 0:2] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        blk[..., 2:] = rng.integers(0, 256, size=(nrows, nb, 20), dtype=np.uint8)          # qh, qs[16]
+        return blk.reshape(nrows, nb * 22)
     if ty == 13:                                             # Q5_K: value = d*sc*q - dmin*m, q in [0, 31]: E[sc*q] = 488, std ~ 420
         nb = K // 256
         blk = np.empty((nrows, nb, 176), dtype=np.uint8)

@@ -700,7 +700,7 @@ def test_mul_mat_image_quants_vs_reference_backend(pkg, be, ref_be, name, M, K, 
 @pytest.mark.parametrize("name", ["q4_0", "q5_0"])
 @pytest.mark.parametrize("M,K,N", [(48, 512, 1), (130, 1024, 5), (257, 96, 8), (33, 4096, 3), (4096, 4096, 1)])
 def test_mul_mat_q4_0_q5_0_integer_path(pkg, be, ref_be, name, M, K, N):
-    """Q4_0 / Q5_0 weights up to 8 columns: integer mat-vec on Q8_0 activation images (k_mmv_q40) -- the integers of
+    """Q4_0 / Q5_0 weights up to 8 columns: integer mat-vec on Q8_0 activation images (k_mmv_blocks<q40_form>) -- the integers of
     ggml_vec_dot_q4_0_q8_0 / _q5_0_q8_0, f32 re-association only against the reference CPU backend"""
     rng = np.random.default_rng(M + K + N)
     wv = _random_image_quant_rows(rng, name, M, K)

@@ -1,5 +1,5 @@
 """IQ4_NL / IQ4_XS weights on the GPU (-m gpu): supports_op admits them, GET_ROWS de-quantises them bit for bit, MUL_MAT up to 8 columns
-runs the integer mat-vec kernels (k_mmv_iq4nl on Q8_0 activation images, k_mmv_iq4xs on Q8_K images: the integers of
+runs the integer mat-vec kernels (k_mmv_blocks with iq4nl_form on Q8_0 activation images, with iq4xs_form on Q8_K images: the integers of
 ggml_vec_dot_iq4_nl_q8_0 / _iq4_xs_q8_K, f32 re-association only), from 9 columns on the F16-image GEMM; and the reference's libllama
 keeps every layer of an IQ4 model on the plug-in.  Everything is compared with the reference CPU backend at test time."""
 import os

@@ -1,5 +1,5 @@
-"""Q4_1 / Q5_1 / Q2_K / Q3_K weights on the GPU (-m gpu): MUL_MAT up to 8 columns runs the integer mat-vec kernels (k_mmv_q41 on Q8_1
-activation images, k_mmv_q2k / k_mmv_q3k on Q8_K images: the integers of ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1 / _q2_K_q8_K / _q3_K_q8_K,
+"""Q4_1 / Q5_1 / Q2_K / Q3_K weights on the GPU (-m gpu): MUL_MAT up to 8 columns runs the integer mat-vec kernels (k_mmv_blocks with q41_form on Q8_1
+activation images, with q2k_form / q3k_form on Q8_K images: the integers of ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1 / _q2_K_q8_K / _q3_K_q8_K,
 f32 re-association only) and builds no F16 image of the weights; from 9 columns on the F16-image GEMM as before; a decode graph and the
 reference's libllama stay on the plug-in.  Everything is compared with the reference CPU backend at test time."""
 import os

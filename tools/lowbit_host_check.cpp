@@ -3,9 +3,9 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
 //       tools/lowbit_host_check.cpp -o /tmp/lowbit_host_check && /tmp/lowbit_host_check
 // It allocates every buffer at exactly the size the library allocates and touches every byte range the kernels touch:
-//   * the Q8_1 image (q81_image_bytes): the quantiser's stores (k_quantize_q81) and the loads of k_mmv_q41 for every block of every column;
-//   * the Q8_K image as k_mmv_q2k / k_mmv_q3k read it (qs, the bsums vector of a half, d);
-//   * a weight matrix of nrows rows: the clamped per-lane loads of the four kernels, last block of the last row included.
+//   * the Q8_1 image (q81_image_bytes): the quantiser's stores (k_quantize_q81) and the loads of q41_form (k_mmv_blocks, mmvq.hip) for every block of every column;
+//   * the Q8_K image as q2k_form / q3k_form read it (qs, the bsums vector of a half, d);
+//   * a weight matrix of nrows rows: the frame's clamped block index and row with the per-lane loads of the four forms, last block of the last row included.
 #include "../llama.cpp-omni_amd/csrc/common.hpp"
 #include <cstring>
 #include <vector>
@@ -28,7 +28,7 @@ static void check_q81_image(int64_t K, int ncols) {
             memcpy(im + K + ib * 4, &d, 4);
             memcpy(im + K + (nb + ib) * 4, &s, 4);
         }
-        for (int64_t ib = 0; ib < nb; ++ib)                                              // k_mmv_q41, both lane halves
+        for (int64_t ib = 0; ib < nb; ++ib)                                              // q41_form::read, both lane halves
             for (int hf = 0; hf < 2; ++hf) {
                 touch(act, (size_t) c * img + ib * 32 + 8 * hf, 8); touch(act, (size_t) c * img + ib * 32 + 16 + 8 * hf, 8);
                 touch(act, (size_t) c * img + K + ib * 4, 4);       touch(act, (size_t) c * img + K + (nb + ib) * 4, 4);
