@@ -14,7 +14,7 @@ if [ -z "$OLD" ]; then
     WT=$(mktemp -d) && git worktree add --detach "$WT" HEAD~1 > /dev/null && make -C "$WT/llama.cpp-omni_amd/csrc" -j16 > "$OUT/parent_build.log" 2>&1 || { echo "parent build failed"; exit 1; }
     OLD=$WT/llama.cpp-omni_amd/lib/libggml-mi355x.so
 fi
-FILES="test_exec_state_gpu test_gpu_parity test_t2w_gpu test_round2_gpu test_round3_gpu test_round4_gpu test_round5_gpu test_round6_gpu test_prefill_kernels_gpu test_iq4_gpu"
+FILES="test_exec_state_gpu test_gpu_parity test_t2w_gpu test_round2_gpu test_round3_gpu test_round4_gpu test_round5_gpu test_round6_gpu test_prefill_kernels_gpu test_iq4_gpu test_fattn_plan_gpu"
 REP=$OUT/launch_log_ab.txt
 echo "launch logs, parent library vs this tree (lines parent / lines new / verdict)" > "$REP"
 # the tests of a module that reach `subprocess` -- directly, through a helper or through a fixture
