@@ -409,6 +409,8 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmv_q51_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q5_1);
     if (!strcmp(key, "mmv_q2k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q2_K);
     if (!strcmp(key, "mmv_q3k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q3_K);
+    if (!strcmp(key, "mmv_id_launches"))    return (double) mi::mmv_id_launches();
+    if (!strcmp(key, "argsort_launches"))   return (double) mi::argsort_launches();
     if (!strncmp(key, "prof_", 5)) {
         std::string k(key + 5);
         const size_t us = k.rfind("_us"), nn = k.rfind("_n"), by = k.rfind("_bytes");

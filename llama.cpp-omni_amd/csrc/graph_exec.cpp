@@ -491,6 +491,27 @@ void compute_node(exec_state & s, int i) {
             if (s.va.cast && (n->src[0] == s.va.cast || g->nodes[i]->src[1]->op == GGML_OP_SOFT_MAX)) materialise_vt(s);
             exec_mul_mat(s, i);
             return;
+        case GGML_OP_MUL_MAT_ID: {                                       // expert mat-vecs, one (slot, token) pair per workgroup column (mmvk.hip k_mmv_id)
+            const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
+            const mm_id_route r = route_mul_mat_id(n);
+            if (!r.ok) { log_msg(GGML_LOG_LEVEL_ERROR, "[mi355x] graph_compute: MUL_MAT_ID %s reached the backend but has no kernel -- supports_op bug\n", n->name); abort(); }
+            for (const ggml_tensor * t = b; t; t = view_parent(t)) settle(s, { t });      // (b is a reshape of the FFN norm's result)
+            // the up and gate nodes of an expert FFN read the same b: the second finds the first's images through s.act (same tensor, same strides)
+            prepare_act(s, b, r.act);                                     // image (t * b->ne[1] + i1) of column (i1, t), flat or token by token
+            mmv_id_args a;
+            a.type = as->type; a.as = as->data; a.as_nb1 = as->nb[1]; a.as_nb2 = as->nb[2]; a.n_expert = as->ne[2];
+            a.ids = ids->data; a.ids_nb0 = ids->nb[0]; a.ids_nb1 = ids->nb[1]; a.n_ids = ids->ne[0]; a.n_tokens = ids->ne[1];
+            a.act = s.c->act_scratch; a.b_ne1 = b->ne[1];
+            a.dst = (float *) n->data; a.dst_nb1 = n->nb[1]; a.dst_nb2 = n->nb[2]; a.K = as->ne[0]; a.nrows = as->ne[1];
+            prof_scope ps(s, "mmv_id", (double) (ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
+            mmv_id_kquant(a, s.st); ++s.n_kernels;
+            break;
+        }
+        case GGML_OP_ARGSORT: {
+            prof_scope ps(s, "argsort", 0);
+            argsort_f32(td(n->src[0]), (int *) n->data, op_param_i32(n, 0) == 1, s.st); ++s.n_kernels;
+            break;
+        }
         case GGML_OP_IM2COL: {
             prof_scope ps(s, "im2col", 0);
             im2col_f32(td(n->src[0]), td(n->src[1]), td(n), n->type, n->op_params, s.st); ++s.n_kernels;

@@ -188,6 +188,9 @@ struct mm_route {
     int64_t  k_head_sized;   // what graph_gemm_partial_need reserves split-K scratch for: k_head's shape rule alone, on any path behind the F16 GEMM's
 };
 mm_route route_mul_mat(const ggml_tensor * n);
+// ... and a MUL_MAT_ID node: admitted or not (supports_op), and the image of b's columns its one path reads (scratch sizing, op_mul_mat_id)
+struct mm_id_route { bool ok; act_kind act; };
+mm_id_route route_mul_mat_id(const ggml_tensor * n);
 // one row per admitted weight type (null: none; BF16 has a path of its own): the image its mat-vec kernels read, their launcher (up to 8 columns) and profile class
 struct mmv_row { int type; act_kind act; void (*launch)(const mmv_args &, hipStream_t); const char * cls; };
 const mmv_row * mmv_row_for(int wtype);

@@ -39,6 +39,11 @@ bool supports_op(const ggml_tensor * op) {
             }
             return true;
         }
+        case GGML_OP_MUL_MAT_ID:
+            return route_mul_mat_id(op).ok;
+        case GGML_OP_ARGSORT:                                 // one workgroup's LDS holds the padded row (argsort.hip); rows are read through nb1..nb3
+            return s0 && s0->type == GGML_TYPE_F32 && op->type == GGML_TYPE_I32 && s0->nb[0] == 4 && is_contiguous(op) && same_shape(s0, op) && argsort_ok(s0->ne[0]) &&
+                   (op_param_i32(op, 0) == 0 || op_param_i32(op, 0) == 1);      // enum ggml_sort_order (ggml.h): ASC = 0, DESC = 1
         case GGML_OP_ADD: case GGML_OP_SUB: case GGML_OP_MUL: case GGML_OP_DIV:
             return s0 && s1 && s0->type == GGML_TYPE_F32 && s1->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 &&
                    same_shape(s0, op) && can_repeat(s1, s0);
@@ -277,6 +282,28 @@ mm_route route_mul_mat(const ggml_tensor * n) {
     if (mmq_takes(n)) { r.path = MM_MMQ; return r; }                                  // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
     return r;                                                                         // the type's own mat-vec kernels, on the blocks (w_image only ever with the GEMM)
 }
+// The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]): one path, the per-pair mat-vec of mmvk.hip at every token
+// count, for K-quant experts.  F16 / F32 / BF16 / MXFP4 experts and the 32-weight block forms have no kernel with the id indirection: refused, they stay on the CPU.
+mm_id_route route_mul_mat_id(const ggml_tensor * n) {
+    mm_id_route r = { false, ACT_NONE };
+    const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
+    if (!as || !b || !ids) return r;
+    const int t = as->type;
+    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K) return r;
+    if (b->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32) return r;
+    if (as->nb[0] != type_size(t) || b->nb[0] != 4 || n->nb[0] != 4 || ids->nb[0] % 4 != 0 || ids->nb[1] % 4 != 0 || b->nb[1] % 4 != 0) return r;
+    if (as->ne[3] != 1 || b->ne[3] != 1 || ids->ne[2] != 1 || ids->ne[3] != 1 || n->ne[3] != 1) return r;                 // the asserts of ggml_mul_mat_id (ggml.c:3088-3096)
+    if (as->ne[0] != b->ne[0] || ids->ne[1] != b->ne[2] || b->ne[1] < 1 || ids->ne[0] % b->ne[1] != 0 || as->ne[2] < 1) return r;
+    if (n->ne[0] != as->ne[1] || n->ne[1] != ids->ne[0] || n->ne[2] != b->ne[2]) return r;
+    if (ids->ne[0] > 65535 || b->ne[2] > 65535 || as->ne[2] > INT32_MAX || as->ne[1] > INT32_MAX) return r;                // grid y / z
+    const int64_t K = as->ne[0];
+    if (K % 256 != 0 || K > INT32_MAX || q8k_image_bytes(K) > (size_t) 152 * 1024) return r;                              // one column's image in LDS
+    if (as->nb[1] < row_size(t, K)) return r;
+    const size_t al = t == GGML_TYPE_Q6_K ? 2 : 16;                                                                       // the vector loads' row alignment, as MUL_MAT -- for every expert's rows
+    if (as->nb[1] % al != 0 || as->nb[2] % al != 0) return r;
+    r.ok = true; r.act = ACT_Q8K;
+    return r;
+}
 bool mm_uses_mmq(const ggml_tensor * n)       { return route_mul_mat(n).path == MM_MMQ; }
 bool mm_uses_mmq_tile(const ggml_tensor * n)  { return route_mul_mat(n).path == MM_MMQ_TILE; }
 bool mm_takes_gemm_any(const ggml_tensor * n) { return route_mul_mat(n).path == MM_GEMM_ANY; }
@@ -293,6 +320,11 @@ size_t graph_act_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
+        if (n->op == GGML_OP_MUL_MAT_ID && !is_empty(n)) {           // one image per column of b
+            const size_t b = act_image_bytes(route_mul_mat_id(n).act, n->src[1]->ne[0]) * (size_t) (n->src[1]->ne[1] * n->src[1]->ne[2] * n->src[1]->ne[3]);
+            if (b > need) need = b;
+            continue;
+        }
         if (n->op != GGML_OP_MUL_MAT || is_empty(n)) continue;
         const mm_route r = route_mul_mat(n);
         const size_t b = r.path == MM_MMQ_TILE ? mmqt_image_bytes(n->src[1]->ne[0], n->src[1]->ne[1])

@@ -77,6 +77,23 @@ void mmv_kquant_multi(const mmv_multi_args & a, hipStream_t st);
 void mmv_kquant_pair_swiglu(int type, const void * Wg, const void * Wu, size_t w_rs, const void * act, size_t act_cs, float * dst, size_t dst_cs,
                             int64_t K, int64_t nrows, int ncols, hipStream_t st, const mmv_norm * norm = nullptr);
 
+// ---- MUL_MAT_ID on K-quant experts (mmvk.hip k_mmv_id; reference ggml_compute_forward_mul_mat_id, ggml-cpu.c:1484 ff.):
+//     dst[:, i, t] = as[:, :, ids[i, t]] . b[:, i % b_ne1, t]      -- one (slot i, token t) pair per grid (y, z), the mat-vec bodies of mmv_kquant_multi at one column
+// The launch reads the ids from device memory (a captured graph follows new ids at every replay); an id outside [0, n_expert) is clamped into range before it becomes an address.
+struct mmv_id_args {
+    int          type;                         // GGML_TYPE_Q4_K / Q5_K / Q6_K
+    const void * as; size_t as_nb1, as_nb2;    // expert matrices: row stride, expert stride (bytes)
+    int64_t      n_expert;
+    const void * ids; size_t ids_nb0, ids_nb1; // i32 [n_ids, n_tokens], strided (a view of the argsort result)
+    int64_t      n_ids, n_tokens;              // <= 65535 each
+    const void * act;                          // Q8_K images of b's columns: image (t * b_ne1 + i % b_ne1) at that many q8k_image_bytes(K)
+    int64_t      b_ne1;
+    float *      dst; size_t dst_nb1, dst_nb2; // f32 [nrows, n_ids, n_tokens]
+    int64_t      K, nrows;
+};
+void mmv_id_kquant(const mmv_id_args & a, hipStream_t st);
+long mmv_id_launches();
+
 // ---- batch-1 decode form (mmv1.hip): ONE activation column, Q4_K / Q6_K, K a multiple of 256 up to 16384 (whole steps of 4096 at the Qwen3-8B widths, TAIL instances otherwise).  The launch takes the f32
 // activation row itself -- x, or rms_norm(x) * norm_w (the RMS_NORM + MUL nodes in front of src1) -- and every workgroup builds the Q8_K
 // image in its prologue, so no norm / quantise launch precedes it; img != null hands over a ready image (q8k_image_bytes layout) instead.
@@ -187,6 +204,10 @@ void pad_reflect_1d_f32(const tdesc & x, const tdesc & y, int p0, int p1, hipStr
 void arange_f32(float * y, int64_t n, float start, float step, hipStream_t st);                                    // ops.cpp:7762-7783
 void timestep_embedding_f32(const float * ts, const tdesc & y, int64_t n, int dim, int max_period, hipStream_t st);  // ops.cpp:7800-7831
 void sum_rows_f32(const tdesc & x, const tdesc & y, hipStream_t st);                                               // ops.cpp:1399-1430
+// ARGSORT of f32 rows (argsort.hip; ops.cpp:7853-7890): x f32 with nb[0] == 4, rows through nb[1..3]; dst dense i32 of the same shape.  Ties: the lower index first.
+bool argsort_ok(int64_t ne0);                  // the padded row fits one workgroup's LDS (ne0 <= 16384)
+void argsort_f32(const tdesc & x, int * dst, bool desc, hipStream_t st);
+long argsort_launches();
 void conv_transpose_1d_f32(const tdesc & w, int w_type, const tdesc & x, const tdesc & y, int s0, hipStream_t st); // ops.cpp:5952-6122
 void cast_f32_i32(const tdesc & src, bool src_is_f32, const tdesc & dst, hipStream_t st);                          // ops.cpp:555, 558-561
 // CPY / CONT / DUP between f32 / f16 with arbitrary strides (same element count)

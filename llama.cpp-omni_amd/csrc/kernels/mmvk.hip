@@ -567,4 +567,70 @@ void mmv_kquant_pair_swiglu(int type, const void * Wg, const void * Wu, size_t w
 #undef MP_GO2
 }
 
+// =================================================================================================
+// MUL_MAT_ID (mixture-of-experts): dst[:, i, t] = as[:, :, ids[i, t]] . b[:, i % b_ne1, t]
+// (ggml_compute_forward_mul_mat_id, ggml-cpu/ggml-cpu.c:1484 ff.).  Grid x = row workgroups, y = slot i, z = token t: every workgroup reads its ONE id
+// from device memory (so a captured graph follows the ids of each replay), picks the expert's matrix and that column's Q8_K image, and runs the body
+// k_mmv_multi runs at one column -- the same vec_dot integers, the same f32 summation order as a MUL_MAT of that expert.
+// An id outside [0, n_expert) is CLAMPED into range before it becomes an address (the reference asserts): a bad id gives a wrong number, never a stray read.
+// =================================================================================================
+struct mmv_id_dev {
+    const char * as; size_t as_nb1, as_nb2; int n_expert;
+    const char * ids; size_t ids_nb0, ids_nb1;
+    const char * act; int b_ne1;
+    char * dst; size_t dst_nb1, dst_nb2;
+    int K, nrows;
+};
+template <int TYPE, int U>
+__global__ void __launch_bounds__(256) k_mmv_id(const mmv_id_dev a) {
+    const int i = blockIdx.y, t = blockIdx.z;
+    int id = *(const int *) (a.ids + (size_t) i * a.ids_nb0 + (size_t) t * a.ids_nb1);
+    id = id < 0 ? 0 : (id >= a.n_expert ? a.n_expert - 1 : id);
+    id = __builtin_amdgcn_readfirstlane(id);
+    const char * W   = a.as + (size_t) id * a.as_nb2;
+    const char * act = a.act + (size_t) (t * a.b_ne1 + i % a.b_ne1) * q8k_image_bytes(a.K);
+    const mmv_out o  = { a.dst + (size_t) i * a.dst_nb1 + (size_t) t * a.dst_nb2, 0, nullptr, 0 };
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), nwaves = gridDim.x * 4;
+    const act_norm nr = { nullptr, 0, nullptr, 0.0f };
+    if (TYPE == GGML_TYPE_Q4_K)      q4k_body<1, 2, U, false, false>(W, nullptr, a.as_nb1, o, act, 0, a.K, a.nrows, wave, nwaves, nr);
+    else if (TYPE == GGML_TYPE_Q5_K) q4k_body<1, 2, U, false, false, true>(W, nullptr, a.as_nb1, o, act, 0, a.K, a.nrows, wave, nwaves, nr);
+    else                             q6k_body<1, 2, U, false, false>(W, nullptr, a.as_nb1, o, act, 0, a.K, a.nrows, wave, nwaves, nr);
+}
+
+static long g_mmv_id_launches = 0;
+long mmv_id_launches() { return g_mmv_id_launches; }
+
+void mmv_id_kquant(const mmv_id_args & a, hipStream_t st) {
+    if (a.nrows == 0 || a.n_ids == 0 || a.n_tokens == 0) return;
+    const size_t lds = q8k_image_bytes(a.K);
+    if (a.K % 256 != 0 || lds > MMVK_LDS_MAX || a.n_ids > 65535 || a.n_tokens > 65535 || a.n_expert < 1 || a.b_ne1 < 1 ||
+        (a.type != GGML_TYPE_Q4_K && a.type != GGML_TYPE_Q5_K && a.type != GGML_TYPE_Q6_K)) {
+        fprintf(stderr, "[mi355x] mmv_id_kquant: shape / type out of range (type %d, K=%lld, ids %lld x %lld)\n", a.type, (long long) a.K, (long long) a.n_ids, (long long) a.n_tokens); abort();
+    }
+    // grid.x: every row group of one pair resident at once (768 expert rows = 96 four-wave workgroups per slot, 8 slots = 768 workgroups: a decode launch fills the
+    // chip); with many pairs it shrinks so that the whole launch stays near 4 resident rounds of mmv_grid_cap() workgroups -- each workgroup then grid-strides over the
+    // pair's row groups and stages the pair's image once
+    const int64_t pairs = a.n_ids * a.n_tokens;
+    int64_t gx = ((a.nrows + 1) / 2 + 3) / 4;
+    const int64_t budget = (int64_t) mmv_grid_cap() * 4 / pairs;
+    if (gx > budget) gx = budget;
+    if (gx < 1) gx = 1;
+    mmv_id_dev d;
+    d.as = (const char *) a.as; d.as_nb1 = a.as_nb1; d.as_nb2 = a.as_nb2; d.n_expert = (int) a.n_expert;
+    d.ids = (const char *) a.ids; d.ids_nb0 = a.ids_nb0; d.ids_nb1 = a.ids_nb1;
+    d.act = (const char *) a.act; d.b_ne1 = (int) a.b_ne1;
+    d.dst = (char *) a.dst; d.dst_nb1 = a.dst_nb1; d.dst_nb2 = a.dst_nb2;
+    d.K = (int) a.K; d.nrows = (int) a.nrows;
+    const dim3 grid((unsigned) gx, (unsigned) a.n_ids, (unsigned) a.n_tokens);
+    const bool u2 = (a.K / 256 + 7) / 8 >= 2;
+    auto go = [&](auto kern) {
+        if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        kern<<<grid, dim3(256), lds, st>>>(d);
+    };
+    if (a.type == GGML_TYPE_Q4_K)      { if (u2) go(k_mmv_id<GGML_TYPE_Q4_K, 2>); else go(k_mmv_id<GGML_TYPE_Q4_K, 1>); }
+    else if (a.type == GGML_TYPE_Q5_K) { if (u2) go(k_mmv_id<GGML_TYPE_Q5_K, 2>); else go(k_mmv_id<GGML_TYPE_Q5_K, 1>); }
+    else                               { if (u2) go(k_mmv_id<GGML_TYPE_Q6_K, 2>); else go(k_mmv_id<GGML_TYPE_Q6_K, 1>); }
+    ++g_mmv_id_launches;
+}
+
 } // namespace mi

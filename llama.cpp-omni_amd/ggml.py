@@ -12,7 +12,7 @@ import numpy as np
 __all__ = [
     "lib_path", "load_library", "Backend", "backend", "Context", "Tensor",
     "GGML_TYPE_F32", "GGML_TYPE_F16", "GGML_TYPE_Q8_0", "GGML_TYPE_Q4_K", "GGML_TYPE_Q6_K", "GGML_TYPE_I32", "GGML_TYPE_I64",
-    "GGML_BACKEND_BUFFER_USAGE_ANY", "GGML_BACKEND_BUFFER_USAGE_WEIGHTS", "GGML_BACKEND_BUFFER_USAGE_COMPUTE", "GGML_ROPE_TYPE_NORMAL", "GGML_ROPE_TYPE_NEOX", "type_traits", "row_size", "OP", "GLU", "UNARY", "ggml_tensor", "ggml_cgraph",
+    "GGML_BACKEND_BUFFER_USAGE_ANY", "GGML_BACKEND_BUFFER_USAGE_WEIGHTS", "GGML_BACKEND_BUFFER_USAGE_COMPUTE", "GGML_ROPE_TYPE_NORMAL", "GGML_ROPE_TYPE_NEOX", "type_traits", "row_size", "OP", "GLU", "UNARY", "SORT_ORDER", "ggml_tensor", "ggml_cgraph",
 ]
 
 # ------------------------------------------------------------------------------------------------ constants
@@ -34,6 +34,11 @@ class OP:
     POOL_1D = 58
     POOL_2D = 59
     GET_ROWS, SET_ROWS, SOFT_MAX, ROPE, FLASH_ATTN_EXT, UNARY, GLU = 39, 41, 45, 47, 69, 80, 89
+    MUL_MAT_ID, ARGSORT = 29, 67
+
+
+class SORT_ORDER:                      # enum ggml_sort_order (ggml.h)
+    ASC, DESC = 0, 1
 
 
 class GLU:
@@ -641,6 +646,32 @@ class Context:
         assert a.ne[0] == b.ne[0] and b.ne[2] % a.ne[2] == 0 and b.ne[3] % a.ne[3] == 0
         T = self._new(GGML_TYPE_F32, (a.ne[1], b.ne[1], b.ne[2], b.ne[3]))
         return self._op(T, OP.MUL_MAT, [a, b])
+
+    def mul_mat_id(self, as_, b, ids):
+        """ggml_mul_mat_id (ggml.c:3083-3107): as_ [K, M, n_expert], b [K, 1 | n_ids, T], ids [n_ids, T] i32 -> [M, n_ids, T];
+        dst[:, i, t] = as_[:, :, ids[i, t]] . b[:, i % b.ne1, t].  The asserts are the reference's (:3088-3096)."""
+        assert not (as_.nb[0] > as_.nb[1]), "as is transposed"
+        assert ids.type == GGML_TYPE_I32
+        assert as_.ne[3] == 1, "as is 3-D (one matrix per expert)"
+        assert b.ne[3] == 1, "b is 3-D"
+        assert ids.ne[2] == 1 and ids.ne[3] == 1, "ids is 2-D"
+        assert ids.ne[1] == b.ne[2], "one expert list per b row"
+        assert as_.ne[0] == b.ne[0], "can_mul_mat"
+        assert ids.ne[0] % b.ne[1] == 0, "can broadcast"
+        T = self._new(GGML_TYPE_F32, (as_.ne[1], ids.ne[0], b.ne[2], 1))
+        return self._op(T, OP.MUL_MAT_ID, [as_, b, ids])
+
+    def argsort(self, a, order):
+        """ggml_argsort (ggml.c:4973-4986): i32 indices of the sorted rows, same shape; op_params[0] = order"""
+        assert a.ne[0] <= 2 ** 31 - 1
+        T = self._new(GGML_TYPE_I32, a.ne)
+        return self._op(T, OP.ARGSORT, [a], (int(order),))
+
+    def top_k(self, a, k):
+        """ggml_top_k (ggml.c:4990-5004): the descending ARGSORT node plus a view of its first k columns"""
+        assert a.ne[0] >= k
+        r = self.argsort(a, SORT_ORDER.DESC)
+        return self.view_4d(r, k, r.ne[1], r.ne[2], r.ne[3], r.nb[1], r.nb[2], r.nb[3], 0)
 
     def glu_split(self, a, b, glu_op):
         T = self._new(a.type, a.ne)
