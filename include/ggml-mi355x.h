@@ -68,7 +68,8 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
 /* counters: "graph_replays", "graph_captures", "eager_graphs", "kernels_last_graph", "mmq_tile_launches",
  * "mmv_iq4nl_launches", "mmv_iq4xs_launches", "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches" (launches of the
  * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
- * "argsort_launches" (both process-wide; a replayed graph re-runs captured launches without counting them),
+ * "argsort_launches", "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node)
+ * (all four process-wide; a replayed graph re-runs captured launches without counting them),
  * "shadow_bytes", "shadow_tensors", "prof_mmv_q4k_us", "prof_mmv_q4k_n", "prof_mmv_q4k_bytes", ....
  * Returns -1 if unknown. */
 GGML_MI355X_API double mi355x_get_stat(struct ggml_backend * backend, const char * key);

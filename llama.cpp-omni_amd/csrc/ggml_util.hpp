@@ -29,6 +29,7 @@ static inline type_info type_traits(int t) {
         case GGML_TYPE_Q8_K: return {256, 292, "q8_K"};
         case GGML_TYPE_IQ4_NL: return {32, 18, "iq4_nl"};
         case GGML_TYPE_IQ4_XS: return {256, 136, "iq4_xs"};
+        case GGML_TYPE_MXFP4: return {32, 17, "mxfp4"};
         case GGML_TYPE_I8:   return {1, 1, "i8"};
         case GGML_TYPE_I16:  return {1, 2, "i16"};
         case GGML_TYPE_I32:  return {1, 4, "i32"};
@@ -90,7 +91,7 @@ static inline float   op_param_f32(const ggml_tensor * t, int i) { float f; memc
 
 static inline const char * op_name(int op) {
     switch (op) {
-        case GGML_OP_NONE: return "NONE"; case GGML_OP_DUP: return "DUP"; case GGML_OP_ADD: return "ADD"; case GGML_OP_SUB: return "SUB";
+        case GGML_OP_NONE: return "NONE"; case GGML_OP_DUP: return "DUP"; case GGML_OP_ADD: return "ADD"; case GGML_OP_ADD_ID: return "ADD_ID"; case GGML_OP_SUB: return "SUB";
         case GGML_OP_MUL: return "MUL"; case GGML_OP_DIV: return "DIV"; case GGML_OP_RMS_NORM: return "RMS_NORM"; case GGML_OP_MUL_MAT: return "MUL_MAT";
         case GGML_OP_SCALE: return "SCALE"; case GGML_OP_CPY: return "CPY"; case GGML_OP_CONT: return "CONT"; case GGML_OP_RESHAPE: return "RESHAPE";
         case GGML_OP_VIEW: return "VIEW"; case GGML_OP_PERMUTE: return "PERMUTE"; case GGML_OP_TRANSPOSE: return "TRANSPOSE";

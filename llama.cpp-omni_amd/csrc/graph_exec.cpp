@@ -504,7 +504,15 @@ void compute_node(exec_state & s, int i) {
             a.act = s.c->act_scratch; a.b_ne1 = b->ne[1];
             a.dst = (float *) n->data; a.dst_nb1 = n->nb[1]; a.dst_nb2 = n->nb[2]; a.K = as->ne[0]; a.nrows = as->ne[1];
             prof_scope ps(s, "mmv_id", (double) (ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
-            mmv_id_kquant(a, s.st); ++s.n_kernels;
+            if (as->type == GGML_TYPE_MXFP4) mmv_id_mxfp4(a, s.st); else mmv_id_kquant(a, s.st);
+            ++s.n_kernels;
+            break;
+        }
+        case GGML_OP_ADD_ID: {                                           // the per-expert bias behind a MUL_MAT_ID (gpt-oss)
+            const ggml_tensor * ids = n->src[2];
+            for (int k = 0; k < 3; ++k) for (const ggml_tensor * t = n->src[k]; t; t = view_parent(t)) settle(s, { t });      // (no operand may still be a deferred norm's result)
+            prof_scope ps(s, "add_id", 0);
+            add_id_f32(td(n->src[0]), td(n->src[1]), ids->data, ids->nb[0], ids->nb[1], td(n), s.st); ++s.n_kernels;
             break;
         }
         case GGML_OP_ARGSORT: {
@@ -667,9 +675,10 @@ void compute_node(exec_state & s, int i) {
             }
             {
                 prof_scope ps(s, "glu", 0);
+                const float alpha = op_param_f32(n, 2), limit = op_param_f32(n, 3);      // (SWIGLU_OAI only)
                 if (emit16) glu_f32(op_param_i32(n, 0), td(n->src[0]), n->src[1] ? &b : nullptr, op_param_i32(n, 1) != 0, td(n), s.st,
-                                    (uint16_t *) act_begin(s), act_image_bytes(ACT_F16, n->ne[0]), n_users(s, n) > 1);
-                else        glu_f32(op_param_i32(n, 0), td(n->src[0]), n->src[1] ? &b : nullptr, op_param_i32(n, 1) != 0, td(n), s.st);
+                                    (uint16_t *) act_begin(s), act_image_bytes(ACT_F16, n->ne[0]), n_users(s, n) > 1, alpha, limit);
+                else        glu_f32(op_param_i32(n, 0), td(n->src[0]), n->src[1] ? &b : nullptr, op_param_i32(n, 1) != 0, td(n), s.st, nullptr, 0, true, alpha, limit);
             }
             ++s.n_kernels;
             note_write(s, n);

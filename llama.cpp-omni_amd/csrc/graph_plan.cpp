@@ -41,6 +41,13 @@ bool supports_op(const ggml_tensor * op) {
         }
         case GGML_OP_MUL_MAT_ID:
             return route_mul_mat_id(op).ok;
+        case GGML_OP_ADD_ID: {                                // the asserts of ggml_add_id (ggml.c:1985-1988) and ggml_compute_forward_add_id_f32 (ops.cpp:707-723)
+            const ggml_tensor * ids = op->src[2];
+            if (!s0 || !s1 || !ids) return false;
+            if (op->type != GGML_TYPE_F32 || s0->type != GGML_TYPE_F32 || s1->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32) return false;
+            if (s0->nb[0] != 4 || s1->nb[0] != 4 || op->nb[0] != 4 || ids->nb[0] % 4 != 0 || ids->nb[1] % 4 != 0) return false;
+            return s0->ne[0] == s1->ne[0] && s0->ne[1] == ids->ne[0] && s0->ne[2] == ids->ne[1] && same_shape(s0, op) && s1->ne[1] >= 1 && s1->ne[1] <= INT32_MAX && nrows(op) <= INT32_MAX;
+        }
         case GGML_OP_ARGSORT:                                 // one workgroup's LDS holds the padded row (argsort.hip); rows are read through nb1..nb3
             return s0 && s0->type == GGML_TYPE_F32 && op->type == GGML_TYPE_I32 && s0->nb[0] == 4 && is_contiguous(op) && same_shape(s0, op) && argsort_ok(s0->ne[0]) &&
                    (op_param_i32(op, 0) == 0 || op_param_i32(op, 0) == 1);      // enum ggml_sort_order (ggml.h): ASC = 0, DESC = 1
@@ -105,6 +112,7 @@ bool supports_op(const ggml_tensor * op) {
             if (!is_contiguous_1(s0) || !is_contiguous_1(op) || (s1 && (!is_contiguous_1(s1) || s1->type != GGML_TYPE_F32))) return false;
             switch (op_param_i32(op, 0)) {
                 case GGML_GLU_OP_REGLU: case GGML_GLU_OP_GEGLU: case GGML_GLU_OP_SWIGLU: case GGML_GLU_OP_GEGLU_ERF: case GGML_GLU_OP_GEGLU_QUICK: return true;
+                case GGML_GLU_OP_SWIGLU_OAI: return true;                 // alpha = op_params[2], limit = op_params[3] (gpt-oss experts)
                 default: return false;
             }
         }
@@ -282,14 +290,15 @@ mm_route route_mul_mat(const ggml_tensor * n) {
     if (mmq_takes(n)) { r.path = MM_MMQ; return r; }                                  // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
     return r;                                                                         // the type's own mat-vec kernels, on the blocks (w_image only ever with the GEMM)
 }
-// The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]): one path, the per-pair mat-vec of mmvk.hip at every token
-// count, for K-quant experts.  F16 / F32 / BF16 / MXFP4 experts and the 32-weight block forms have no kernel with the id indirection: refused, they stay on the CPU.
+// The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]): one path, the per-pair mat-vec at every token count --
+// mmvk.hip for K-quant experts (Q8_K images), mmv_mxfp4.hip for MXFP4 experts (gpt-oss; Q8_0 images, 17-byte blocks: no row or expert alignment condition).
+// F16 / F32 / BF16 experts and the nine 32-weight block forms of mmvq.hip have no kernel with the id indirection: refused, they stay on the CPU.
 mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     mm_id_route r = { false, ACT_NONE };
     const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
     if (!as || !b || !ids) return r;
     const int t = as->type;
-    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K) return r;
+    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K && t != GGML_TYPE_MXFP4) return r;
     if (b->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32) return r;
     if (as->nb[0] != type_size(t) || b->nb[0] != 4 || n->nb[0] != 4 || ids->nb[0] % 4 != 0 || ids->nb[1] % 4 != 0 || b->nb[1] % 4 != 0) return r;
     if (as->ne[3] != 1 || b->ne[3] != 1 || ids->ne[2] != 1 || ids->ne[3] != 1 || n->ne[3] != 1) return r;                 // the asserts of ggml_mul_mat_id (ggml.c:3088-3096)
@@ -297,6 +306,12 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     if (n->ne[0] != as->ne[1] || n->ne[1] != ids->ne[0] || n->ne[2] != b->ne[2]) return r;
     if (ids->ne[0] > 65535 || b->ne[2] > 65535 || as->ne[2] > INT32_MAX || as->ne[1] > INT32_MAX) return r;                // grid y / z
     const int64_t K = as->ne[0];
+    if (t == GGML_TYPE_MXFP4) {
+        if (K < 32 || K % 32 != 0 || K > INT32_MAX || q80_image_bytes(K) > (size_t) 152 * 1024) return r;                 // one column's Q8_0 image in LDS
+        if (as->nb[1] < row_size(t, K)) return r;
+        r.ok = true; r.act = ACT_Q80;
+        return r;
+    }
     if (K % 256 != 0 || K > INT32_MAX || q8k_image_bytes(K) > (size_t) 152 * 1024) return r;                              // one column's image in LDS
     if (as->nb[1] < row_size(t, K)) return r;
     const size_t al = t == GGML_TYPE_Q6_K ? 2 : 16;                                                                       // the vector loads' row alignment, as MUL_MAT -- for every expert's rows

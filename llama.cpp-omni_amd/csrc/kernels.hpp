@@ -93,6 +93,10 @@ struct mmv_id_args {
 };
 void mmv_id_kquant(const mmv_id_args & a, hipStream_t st);
 long mmv_id_launches();
+// the same on MXFP4 experts (mmv_mxfp4.hip; ggml_vec_dot_mxfp4_q8_0 integers): type = GGML_TYPE_MXFP4, act = Q8_0 images (q80_image_bytes(K) each), K % 32 == 0,
+// 17-byte blocks with no row or expert alignment condition.  Counted apart from the K-quant launches (stat "mmv_id_mxfp4_launches").
+void mmv_id_mxfp4(const mmv_id_args & a, hipStream_t st);
+long mmv_id_mxfp4_launches();
 
 // ---- batch-1 decode form (mmv1.hip): ONE activation column, Q4_K / Q6_K, K a multiple of 256 up to 16384 (whole steps of 4096 at the Qwen3-8B widths, TAIL instances otherwise).  The launch takes the f32
 // activation row itself -- x, or rms_norm(x) * norm_w (the RMS_NORM + MUL nodes in front of src1) -- and every workgroup builds the Q8_K
@@ -181,7 +185,9 @@ void soft_max_f32(const tdesc & x, const tdesc * mask, int mask_type, const floa
                   uint16_t * y16 = nullptr, size_t y16_rs = 0, bool write_f32 = true);      // y16: also / only the f16 rows (the next MUL_MAT's activation image); needs soft_max_rows_ok
 bool soft_max_rows_ok(const tdesc & x, const tdesc * mask, int mask_type, const float * sinks, const tdesc & y);
 // GLU (split or single-tensor forms; ops.cpp:2934-2990 for swiglu)
-void glu_f32(int glu_op, const tdesc & a, const tdesc * b, bool swapped, const tdesc & y, hipStream_t st, uint16_t * y16 = nullptr, size_t y16_rs = 0, bool write_f32 = true);
+// (alpha, limit: op_params[2], [3] of GGML_GLU_OP_SWIGLU_OAI -- ops.cpp:3077-3142; the other ops ignore them)
+void glu_f32(int glu_op, const tdesc & a, const tdesc * b, bool swapped, const tdesc & y, hipStream_t st, uint16_t * y16 = nullptr, size_t y16_rs = 0, bool write_f32 = true,
+             float alpha = 0.0f, float limit = 0.0f);
 // SWIGLU (split form) straight into the Q8_K activation images of its rows (+ optionally the f32 result): the GLU of an FFN whose
 // down projection is a K-quant mat-mul at several columns
 bool swiglu_q8k_ok(const tdesc & a, const tdesc & b, const tdesc & y);
@@ -190,6 +196,10 @@ void swiglu_q8k(const tdesc & a, const tdesc & b, const tdesc & y, bool write_f3
 void unary_f32(int uop, const float * x, float * y, int64_t n, hipStream_t st, uint16_t * y16 = nullptr, bool write_f32 = true);   // y16: dense f16 copy of the result (n % 4 == 0, aligned)
 // ADD / SUB / MUL / DIV with ggml broadcast semantics (src1 repeats over src0)
 void bin_bcast_f32(int op, const tdesc & a, const tdesc & b, const tdesc & y, hipStream_t st);
+// ADD_ID (ops.cpp:699-748): y[:, i1, i2, i3] = a[:, i1, i2, i3] + b[:, ids[i1, i2]] -- the per-expert bias behind a MUL_MAT_ID.  f32 rows read through their strides; ids i32,
+// read from device memory through ids_nb0 / ids_nb1 and clamped into [0, b.ne[1]) before they become an address (the reference asserts)
+void add_id_f32(const tdesc & a, const tdesc & b, const void * ids, size_t ids_nb0, size_t ids_nb1, const tdesc & y, hipStream_t st);
+long add_id_launches();
 void scale_f32(const float * x, float * y, int64_t n, float s, float b, hipStream_t st);
 // ---- ops of the Token2Wav graphs (kernels/t2w_ops.hip; reference tools/omni/token2wav/token2wav-impl.cpp)
 // SQR / SQRT / LOG / SIN / COS / CLAMP(p0 = min, p1 = max) / LEAKY_RELU(p0 = slope) on dense f32

@@ -880,7 +880,20 @@ void swiglu_q8k(const tdesc & a, const tdesc & b, const tdesc & y, bool write_f3
                                                                          write_f32 ? (char *) y.p : nullptr, (int64_t) y.nb[1], (char *) img, q8k_image_bytes(y.ne[0]), nblk, total);
 }
 
-void glu_f32(int glu_op, const tdesc & a, const tdesc * b, bool swapped, const tdesc & y, hipStream_t st, uint16_t * y16, size_t y16_rs, bool write_f32) {
+// SWIGLU_OAI (ggml_compute_forward_swiglu_oai_f32, ops.cpp:3077-3142; gpt-oss experts): x = min(a, limit), g = clamp(b, -limit, limit), x / (1 + expf(alpha * -x)) * (g + 1)
+__global__ void __launch_bounds__(256) k_swiglu_oai(const char * __restrict__ a, int64_t a_rs, const char * __restrict__ b, int64_t b_rs, char * __restrict__ y, int64_t y_rs,
+                                                   int64_t nc, int64_t nr, char * __restrict__ y16, int64_t y16_rs, float alpha, float limit) {
+    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nc * nr) return;
+    const int64_t r = t / nc, i = t % nc;
+    const float x = fminf(((const float *) (a + r * a_rs))[i], limit);
+    const float g = fminf(fmaxf(((const float *) (b + r * b_rs))[i], -limit), limit);
+    const float v = x / (1.0f + expf(alpha * (-x))) * (g + 1.0f);
+    if (y)   ((float *) (y + r * y_rs))[i] = v;
+    if (y16) ((uint16_t *) (y16 + r * y16_rs))[i] = f2h(v);
+}
+
+void glu_f32(int glu_op, const tdesc & a, const tdesc * b, bool swapped, const tdesc & y, hipStream_t st, uint16_t * y16, size_t y16_rs, bool write_f32, float alpha, float limit) {
     // rows are contiguous_1 (checked by supports_op): treat as [nc, nr] with a row stride
     const int64_t nc = y.ne[0];
     const int64_t nr = y.ne[1] * y.ne[2] * y.ne[3];
@@ -895,7 +908,36 @@ void glu_f32(int glu_op, const tdesc & a, const tdesc * b, bool swapped, const t
                                                                                               (int) (nc / 4), (char *) y16, (int64_t) y16_rs);
         return;
     }
+    if (glu_op == GGML_GLU_OP_SWIGLU_OAI) {
+        k_swiglu_oai<<<dim3((unsigned) ((nc * nr + 255) / 256)), dim3(256), 0, st>>>(ap, a_rs, bp, b_rs, write_f32 ? (char *) y.p : nullptr, (int64_t) y.nb[1], nc, nr, (char *) y16, (int64_t) y16_rs, alpha, limit);
+        return;
+    }
     k_glu<<<dim3((unsigned) ((nc * nr + 255) / 256)), dim3(256), 0, st>>>(glu_op, ap, a_rs, bp, b_rs, write_f32 ? (char *) y.p : nullptr, (int64_t) y.nb[1], nc, nr, (char *) y16, (int64_t) y16_rs);
+}
+
+// ADD_ID (ggml_compute_forward_add_id_f32, ops.cpp:699-748): one workgroup per row (i1, i2, i3) of a; it reads the row's id from device memory, clamps it into
+// [0, n_b) before it becomes an address, and adds row `id` of b.  One f32 add per element: the reference's value bit for bit.
+__global__ void __launch_bounds__(256) k_add_id(const char * __restrict__ a, size_t a_nb1, size_t a_nb2, size_t a_nb3, const char * __restrict__ b, size_t b_nb1, int n_b,
+                                               const char * __restrict__ ids, size_t ids_nb0, size_t ids_nb1, char * __restrict__ y, size_t y_nb1, size_t y_nb2, size_t y_nb3,
+                                               int ne0, int ne1, int ne2) {
+    const int r = blockIdx.x;
+    const int i3 = r / (ne2 * ne1), i2 = (r - i3 * ne2 * ne1) / ne1, i1 = r - i3 * ne2 * ne1 - i2 * ne1;
+    int id = *(const int *) (ids + (size_t) i1 * ids_nb0 + (size_t) i2 * ids_nb1);
+    id = id < 0 ? 0 : (id >= n_b ? n_b - 1 : id);
+    const float * ap = (const float *) (a + (size_t) i1 * a_nb1 + (size_t) i2 * a_nb2 + (size_t) i3 * a_nb3);
+    const float * bp = (const float *) (b + (size_t) id * b_nb1);
+    float *       yp = (float *) (y + (size_t) i1 * y_nb1 + (size_t) i2 * y_nb2 + (size_t) i3 * y_nb3);
+    for (int i = threadIdx.x; i < ne0; i += 256) yp[i] = ap[i] + bp[i];
+}
+static long g_add_id_launches = 0;
+long add_id_launches() { return g_add_id_launches; }
+void add_id_f32(const tdesc & a, const tdesc & b, const void * ids, size_t ids_nb0, size_t ids_nb1, const tdesc & y, hipStream_t st) {
+    const int64_t nr = a.ne[1] * a.ne[2] * a.ne[3];
+    if (nr == 0 || a.ne[0] == 0) return;
+    if (nr > INT32_MAX || a.ne[0] > INT32_MAX || b.ne[1] < 1 || b.ne[1] > INT32_MAX) { fprintf(stderr, "[mi355x] add_id: shape out of range\n"); abort(); }
+    k_add_id<<<dim3((unsigned) nr), dim3(256), 0, st>>>((const char *) a.p, a.nb[1], a.nb[2], a.nb[3], (const char *) b.p, b.nb[1], (int) b.ne[1], (const char *) ids, ids_nb0, ids_nb1,
+                                                        (char *) y.p, y.nb[1], y.nb[2], y.nb[3], (int) a.ne[0], (int) a.ne[1], (int) a.ne[2]);
+    ++g_add_id_launches;
 }
 
 static __device__ __forceinline__ float unary_apply(int op, float v) {

@@ -20,6 +20,7 @@ GGML_TYPE_F32, GGML_TYPE_F16, GGML_TYPE_Q8_0 = 0, 1, 8
 GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_K = 12, 14, 15
 GGML_TYPE_I32, GGML_TYPE_I64 = 26, 27
 GGML_TYPE_IQ4_NL, GGML_TYPE_IQ4_XS = 20, 23
+GGML_TYPE_MXFP4 = 39                      # {uint8 e (E8M0); uint8 qs[16]}: 32 weights in 17 bytes (ggml-common.h block_mxfp4)
 GGML_ROPE_TYPE_NORMAL, GGML_ROPE_TYPE_NEOX = 0, 2
 GGML_PREC_F32 = 10
 GGML_BACKEND_BUFFER_USAGE_ANY, GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_BACKEND_BUFFER_USAGE_COMPUTE = 0, 1, 2   # ggml-backend.h:49-53
@@ -35,6 +36,7 @@ class OP:
     POOL_2D = 59
     GET_ROWS, SET_ROWS, SOFT_MAX, ROPE, FLASH_ATTN_EXT, UNARY, GLU = 39, 41, 45, 47, 69, 80, 89
     MUL_MAT_ID, ARGSORT = 29, 67
+    ADD_ID = 3
 
 
 class SORT_ORDER:                      # enum ggml_sort_order (ggml.h)
@@ -55,7 +57,7 @@ _TRAITS = {  # type -> (block elements, block bytes, numpy dtype or None)
     GGML_TYPE_I32: (1, 4, np.int32), GGML_TYPE_I64: (1, 8, np.int64),
     2: (32, 18, None), 3: (32, 20, None), 6: (32, 22, None), 7: (32, 24, None),      # Q4_0 Q4_1 Q5_0 Q5_1
     10: (256, 84, None), 11: (256, 110, None), 13: (256, 176, None),                # Q2_K Q3_K Q5_K
-    GGML_TYPE_IQ4_NL: (32, 18, None), GGML_TYPE_IQ4_XS: (256, 136, None),
+    GGML_TYPE_IQ4_NL: (32, 18, None), GGML_TYPE_IQ4_XS: (256, 136, None), GGML_TYPE_MXFP4: (32, 17, None),
     30: (1, 2, np.uint16),                                                          # BF16 (as raw 16-bit words)
 }
 
@@ -516,6 +518,16 @@ class Context:
     def add(self, a, b):
         return self._bin(OP.ADD, a, b)
 
+    def add_id(self, a, b, ids):
+        """ggml_add_id (ggml.c:1979-1998): a [n, n_used, T], b [n, n_mats], ids [n_used, T] i32 -> a's shape; dst[:, i1, i2] = a[:, i1, i2] + b[:, ids[i1, i2]].
+        The asserts are the reference's (:1985-1988)."""
+        assert a.ne[0] == b.ne[0]
+        assert a.ne[1] == ids.ne[0]
+        assert a.ne[2] == ids.ne[1]
+        assert ids.type == GGML_TYPE_I32
+        T = self._new(a.type, a.ne)
+        return self._op(T, OP.ADD_ID, [a, b, ids])
+
     def sub(self, a, b):
         return self._bin(OP.SUB, a, b)
 
@@ -676,6 +688,29 @@ class Context:
     def glu_split(self, a, b, glu_op):
         T = self._new(a.type, a.ne)
         return self._op(T, OP.GLU, [a, b], (glu_op, 0))
+
+    def swiglu_oai(self, a, b, alpha, limit, swapped=False):
+        """ggml_swiglu_oai (ggml.c:2873-2884): the split GLU with alpha / limit in op_params[2] / [3]; the asserts are ggml_glu_impl's (:2731-2737).
+        b None: the single-tensor form (ggml_glu_impl without b), `swapped` as ggml_glu's argument."""
+        def contiguous_1(t):                                          # ggml_is_contiguous_n(t, 1): rows may be strided, the dimensions above are dense
+            blck, size, _ = _TRAITS[t.type]
+            if t.ne[0] != blck and t.nb[0] != size:
+                return False
+            nb = t.nb[1] * t.ne[1] if t.ne[1] != 1 else size * (t.ne[0] // blck)
+            for i in (2, 3):
+                if t.ne[i] != 1:
+                    if t.nb[i] != nb:
+                        return False
+                    nb *= t.ne[i]
+            return True
+        assert contiguous_1(a)
+        if b is not None:
+            assert contiguous_1(b)
+            assert tuple(a.ne) == tuple(b.ne)
+            assert a.type == b.type
+        T = self.glu_split(a, b, GLU.SWIGLU_OAI) if b is not None else self.glu(a, GLU.SWIGLU_OAI, swapped)
+        T.t.op_params[2], T.t.op_params[3] = _f32_bits(alpha), _f32_bits(limit)
+        return T
 
     def swiglu_split(self, a, b):
         return self.glu_split(a, b, GLU.SWIGLU)

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from .ggml import (GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_ROPE_TYPE_NEOX, GGML_TYPE_F16, GGML_TYPE_F32, GGML_TYPE_I32, GGML_TYPE_I64, GGML_TYPE_IQ4_NL,
-                   GGML_TYPE_IQ4_XS, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_0, Context, row_size)
+                   GGML_TYPE_IQ4_XS, GGML_TYPE_MXFP4, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_0, Context, row_size)
 
 QWEN3_8B = dict(n_embd=4096, n_layer=36, n_head=32, n_head_kv=8, head_dim=128, n_ff=12288, n_vocab=151936,
                 rms_eps=1e-6, rope_base=1e6, n_ctx_orig=40960)
@@ -162,6 +162,13 @@ def random_blocks(rng, ty, nrows, K, std=0.02):
         blk[..., :108] = rng.integers(0, 256, size=(nrows, nb, 108), dtype=np.uint8)       # hmask[32], qs[64], scales[12]
         blk[..., 108:110] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
         return blk.reshape(nrows, nb * 110)
+    if ty == GGML_TYPE_MXFP4:                                # {e, qs[16]}: value = kvalues_mxfp4[q] * 2^(e - 128), rms of the table ~ 5.85
+        nb = K // 32
+        blk = np.empty((nrows, nb, 17), dtype=np.uint8)
+        e0 = 128 + int(np.round(np.log2(std / 5.85)))
+        blk[..., 0] = np.clip(e0 + rng.integers(-1, 2, size=(nrows, nb)), 0, 254).astype(np.uint8)
+        blk[..., 1:] = rng.integers(0, 256, size=(nrows, nb, 16), dtype=np.uint8)
+        return blk.reshape(nrows, nb * 17)
     raise ValueError(ty)
 
 

@@ -1,0 +1,333 @@
+"""The three ops a gpt-oss expert layer adds, on the GPU (`-m gpu`): MUL_MAT_ID on MXFP4 experts (kernels/mmv_mxfp4.hip), ADD_ID and GLU / SWIGLU_OAI
+(kernels/elementwise.hip), and the reference's build_moe_ffn block as llm_build_openai_moe_iswa calls it (llama.cpp-omni_amd/gptoss.py) -- each through the backend
+C-ABI and against the reference CPU backend (oracle/ref_backend.py) on the same bytes.
+
+Bars: MXFP4 MUL_MAT_ID -- NMSE <= 1e-9, the project's bar for integer mat-vecs against the same integers (every output is the reference's vec_dot_mxfp4_q8_0: the
+same int8 products and power-of-two scales, only the order of the f32 additions over the blocks differs).  ADD_ID -- the reference's bits: one f32 add per element.
+SWIGLU_OAI -- NMSE <= 1e-7, the default of the reference's own harness (test-backend-ops max_nmse_err).  The block -- the selected ids equal, the output inside the
+reference's own bar for MUL_MAT_ID in test-backend-ops (NMSE 5e-4).
+No test feeds an out-of-range id: the kernels clamp them, the reference asserts."""
+import numpy as np
+import pytest
+
+from conftest import nmse
+
+pytestmark = pytest.mark.gpu
+
+F32, F16, I32, MXFP4 = 0, 1, 26, 39
+
+
+def _compute(be_, c, outs, feeds):
+    c.alloc()
+    for t, v in feeds:
+        be_.tensor_set(t, v)
+    be_.graph_compute(c.graph())
+    res = [be_.tensor_get(o).copy() for o in outs]
+    c.free()
+    return res
+
+
+# ------------------------------------------------------------------------------------------------ supports_op
+def _mmid_node(pkg, be, ty, K, M=64, n_expert=8, n_used=4, T=3, K_decl=None):
+    c = pkg.Context(be)
+    as_ = c.new_tensor(ty, K, M, n_expert)
+    b = c.new_tensor(F32, K, 1, T)
+    if K_decl is not None:                                            # a row length the constructors refuse: declared on tensors that own room for more
+        as_.t.ne[0] = K_decl
+        b.t.ne[0] = K_decl
+    ids = c.view_2d(c.new_tensor(I32, n_expert, T), n_used, T, n_expert * 4, 0)
+    return c, c.mul_mat_id(as_, b, ids)
+
+
+def _supported(be, c, y):
+    c.alloc()
+    ok = be.supports_op(y)
+    c.free()
+    return ok
+
+
+@pytest.mark.parametrize("K", [32, 288, 2880])
+def test_supports_op_mul_mat_id_mxfp4(pkg, be, K):
+    assert _supported(be, *_mmid_node(pkg, be, MXFP4, K))
+
+
+def test_supports_op_add_id(pkg, be):
+    c = pkg.Context(be)
+    ids = c.view_2d(c.new_tensor(I32, 8, 5), 4, 5, 32, 0)
+    assert _supported(be, c, c.add_id(c.new_tensor(F32, 288, 4, 5), c.new_tensor(F32, 288, 8), ids))
+
+
+def test_supports_op_swiglu_oai_split_and_single(pkg, be):
+    c = pkg.Context(be)
+    y = c.swiglu_oai(c.new_tensor(F32, 288, 4, 5), c.new_tensor(F32, 288, 4, 5), 1.702, 7.0)
+    assert _supported(be, c, y)
+    for swapped in (False, True):
+        c = pkg.Context(be)
+        assert _supported(be, c, c.swiglu_oai(c.new_tensor(F32, 576, 4, 5), None, 1.702, 7.0, swapped=swapped))
+
+
+def test_supports_op_still_refuses(pkg, be):
+    assert not _supported(be, *_mmid_node(pkg, be, MXFP4, 64, K_decl=48))           # K no multiple of the 32-weight block
+    assert not _supported(be, *_mmid_node(pkg, be, F16, 256))                      # F16 experts: no kernel with the id indirection
+    c = pkg.Context(be)
+    assert not _supported(be, c, c.mul_mat(c.new_tensor(MXFP4, 288, 64), c.new_tensor(F32, 288, 3)))      # dense MUL_MAT on MXFP4: out of scope (gpt-oss uses it for experts only)
+
+
+# ------------------------------------------------------------------------------------------------ MXFP4 MUL_MAT_ID
+def _ids(rng, pattern, n_expert, n_used, T):
+    """the WIDE [T, n_expert] i32 tensor the node's ids are a strided view of (its first n_used columns)"""
+    wide = np.stack([rng.permutation(n_expert) for _ in range(T)]).astype(np.int32)
+    if pattern == "last":                                             # every token names expert n_expert - 1 in slot 0
+        for t in range(T):
+            j = int(np.where(wide[t] == n_expert - 1)[0][0])
+            wide[t, [0, j]] = wide[t, [j, 0]]
+    elif pattern == "same":                                           # every pair names the same expert
+        wide[:, :n_used] = 1
+    return wide
+
+
+def _mmid_run(pkg, be_, n_expert, n_used, T, M, K, bcast, wv, bv, idv):
+    c = pkg.Context(be_)
+    as_ = c.new_tensor(MXFP4, K, M, n_expert)
+    b = c.new_tensor(F32, K, 1 if bcast else n_used, T)
+    wide = c.new_tensor(I32, n_expert, T)
+    ids = c.view_2d(wide, n_used, T, wide.nb[1], 0)
+    y = c.mul_mat_id(as_, b, ids)
+    (got,) = _compute(be_, c, [y], [(as_, wv), (b, bv), (wide, idv)])
+    return got.reshape(T, n_used, M)
+
+
+# K: 32 = one block, 17-byte rows; 96 / 288 = 3 / 9 blocks (odd counts: every second row starts at an odd address); 2048 = exactly two 32-block wave steps; 2080 one block
+# past that; 2880 = gpt-oss, 90 blocks (the three-steps-per-row instance).  M = 1 / 3 / 70: less than, one and a half, and many of the 2 rows a wave takes.  Experts / used
+# 4 / 1, 8 / 4, 32 / 4; 1 / 2 / 9 / 33 tokens (33 x 4 pairs: the grid budget shrinks grid.x and the workgroups stride); b broadcast over the slots and per slot; an ids
+# pattern that uses the last expert, one where all pairs name the same expert, random ones
+MMID_CASES = [
+    (4, 1, 1, 1, 32, True, "last"),
+    (8, 4, 9, 1, 32, False, "rand"),
+    (8, 4, 2, 3, 96, False, "rand"),
+    (4, 1, 2, 70, 96, True, "rand"),
+    (32, 4, 9, 70, 288, True, "same"),
+    (8, 4, 33, 70, 288, False, "rand"),
+    (8, 4, 1, 70, 2048, True, "rand"),
+    (32, 4, 33, 3, 2048, True, "last"),
+    (4, 1, 9, 3, 2080, False, "last"),
+    (8, 4, 2, 70, 2080, True, "same"),
+    (32, 4, 1, 70, 2880, True, "rand"),
+    (8, 4, 2, 3, 2880, False, "same"),
+]
+
+
+def _check_mmid(pkg, be, ref_be, what, n_expert, n_used, T, M, K, bcast, wv, bv, idv):
+    n0, k0 = be.get_stat("mmv_id_mxfp4_launches"), be.get_stat("mmv_id_launches")
+    got = _mmid_run(pkg, be, n_expert, n_used, T, M, K, bcast, wv, bv, idv)
+    assert be.get_stat("mmv_id_mxfp4_launches") == n0 + 1             # one launch covers every (slot, token) pair
+    assert be.get_stat("mmv_id_launches") == k0                       # ... and it is not booked with the K-quant launches
+    want = _mmid_run(pkg, ref_be, n_expert, n_used, T, M, K, bcast, wv, bv, idv)
+    assert np.isfinite(want).all(), "the fixture: the reference's own result is finite"
+    e = nmse(got, want)
+    print(f"MUL_MAT_ID mxfp4 {what} experts {n_expert} used {n_used} T {T} M {M} K {K} bcast {bcast}: NMSE {e:.3e}, mean |want| {np.abs(want).mean():.3e}")
+    assert np.isfinite(got).all()
+    assert e <= 1e-9
+    return got, want
+
+
+@pytest.mark.parametrize("n_expert,n_used,T,M,K,bcast,pattern", MMID_CASES, ids=["-".join(str(v) for v in cs) for cs in MMID_CASES])
+def test_mul_mat_id_mxfp4_vs_reference(pkg, be, ref_be, n_expert, n_used, T, M, K, bcast, pattern):
+    from llama_cpp_omni_amd import qwen3
+    rng = np.random.default_rng(n_expert * 1000 + n_used * 100 + T + M + K)
+    wv = qwen3.random_blocks(rng, MXFP4, M * n_expert, K, std=0.05)
+    bv = (rng.standard_normal((T, 1 if bcast else n_used, K)) * rng.choice([0.1, 1.0, 10.0])).astype(np.float32)
+    idv = _ids(rng, pattern, n_expert, n_used, T)
+    _check_mmid(pkg, be, ref_be, pattern, n_expert, n_used, T, M, K, bcast, wv, bv, idv)
+
+
+def test_mul_mat_id_mxfp4_denormal_scales(pkg, be, ref_be):
+    """every block's e is 0 or 1: half the scale is 2^-128 / 2^-127, an f32 DENORMAL.  Activations of amplitude 1e6 give d_y <= 1e6 / 127 (an f16: <= 65504), so the
+    reference's outputs sumi * (d_y * 2^-128) are normal f32 numbers around 2^-100; a kernel that flushes the denormal scale returns zeros"""
+    from llama_cpp_omni_amd import qwen3
+    n_expert, n_used, T, M, K = 8, 4, 2, 70, 288
+    rng = np.random.default_rng(77)
+    wv = qwen3.random_blocks(rng, MXFP4, M * n_expert, K).reshape(M * n_expert, K // 32, 17).copy()
+    wv[..., 0] = rng.integers(0, 2, size=wv.shape[:2])
+    wv = wv.reshape(M * n_expert, -1)
+    bv = rng.uniform(-1e6, 1e6, (T, 1, K)).astype(np.float32)
+    got, want = _check_mmid(pkg, be, ref_be, "e in {0, 1}", n_expert, n_used, T, M, K, True, wv, bv, _ids(rng, "rand", n_expert, n_used, T))
+    big = np.abs(want) >= 2.0 ** -110
+    assert big.mean() > 0.5 and np.abs(want).max() < 2.0 ** -90       # (the fixture: results of about 2^-100, far above the f32 denormal range)
+    assert (got[big] != 0).all()
+
+
+def test_mul_mat_id_mxfp4_largest_scale(pkg, be, ref_be):
+    """one block of every row has e = 254 (half the scale: 2^126) beside ordinary ones; activations of amplitude 0.01 (d_y about 2^-13.6, a normal f16) keep the
+    reference's result finite: |sumi| <= 32 * 127 * 12 < 2^15.6, so one such block stays below 2^128"""
+    from llama_cpp_omni_amd import qwen3
+    n_expert, n_used, T, M, K = 4, 1, 2, 3, 288
+    rng = np.random.default_rng(78)
+    wv = qwen3.random_blocks(rng, MXFP4, M * n_expert, K).reshape(M * n_expert, K // 32, 17).copy()
+    wv[np.arange(M * n_expert), rng.integers(0, K // 32, M * n_expert), 0] = 254
+    wv = wv.reshape(M * n_expert, -1)
+    bv = rng.uniform(-0.01, 0.01, (T, 1, K)).astype(np.float32)
+    bv[..., ::32] = 0.01                                              # every block's amax, so d_y = 0.01 / 127
+    got, want = _check_mmid(pkg, be, ref_be, "e = 254", n_expert, n_used, T, M, K, True, wv, bv, _ids(rng, "rand", n_expert, n_used, T))
+    assert np.abs(want).max() > 2.0 ** 110
+
+
+# ------------------------------------------------------------------------------------------------ ADD_ID
+def _add_id_run(pkg, be_, n, n_mats, n_used, T, av, bv, idv, pad=0):
+    c = pkg.Context(be_)
+    if pad:                                                           # a's rows read through nb1 > n * 4: a view of a wider tensor
+        wide_a = c.new_tensor(F32, n + pad, n_used, T)
+        a = c.view_3d(wide_a, n, n_used, T, wide_a.nb[1], wide_a.nb[2], 0)
+        feed = np.full((T, n_used, n + pad), 1e30, np.float32)
+        feed[..., :n] = av
+        a_feed = (wide_a, feed)
+    else:
+        a = c.new_tensor(F32, n, n_used, T)
+        a_feed = (a, av)
+    b = c.new_tensor(F32, n, n_mats)
+    wide = c.new_tensor(I32, n_mats, T)
+    ids = c.view_2d(wide, n_used, T, wide.nb[1], 0)
+    y = c.add_id(a, b, ids)
+    (got,) = _compute(be_, c, [y], [a_feed, (b, bv), (wide, idv)])
+    return got.reshape(T, n_used, n)
+
+
+# n = 1 (one element), 32, 129 (odd, more than half a workgroup's stride), 2880 (gpt-oss: rows longer than the 256 threads of a workgroup); 4 / 32 bias rows; 1 / 2 / 4 slots;
+# 1 / 33 tokens; pad: a is a view with a wider nb[1]
+ADD_ID_CASES = [(1, 4, 1, 1, 0), (32, 4, 2, 33, 0), (129, 32, 4, 1, 0), (129, 4, 1, 33, 0), (2880, 32, 4, 33, 0), (2880, 4, 2, 1, 0), (32, 32, 4, 33, 0), (129, 32, 4, 33, 7)]
+
+
+@pytest.mark.parametrize("n,n_mats,n_used,T,pad", ADD_ID_CASES, ids=["-".join(str(v) for v in cs) for cs in ADD_ID_CASES])
+def test_add_id_bit_exact(pkg, be, ref_be, n, n_mats, n_used, T, pad):
+    rng = np.random.default_rng(n * 7 + n_mats + n_used * 3 + T)
+    av = rng.standard_normal((T, n_used, n)).astype(np.float32)
+    bv = rng.standard_normal((n_mats, n)).astype(np.float32)
+    idv = _ids(rng, "last" if T == 33 else "rand", n_mats, n_used, T)
+    n0 = be.get_stat("add_id_launches")
+    got = _add_id_run(pkg, be, n, n_mats, n_used, T, av, bv, idv, pad)
+    assert be.get_stat("add_id_launches") == n0 + 1
+    want = _add_id_run(pkg, ref_be, n, n_mats, n_used, T, av, bv, idv, pad)
+    assert np.array_equal(want, av + bv[idv[:, :n_used]])             # (the fixture: the op is this one add)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+# ------------------------------------------------------------------------------------------------ SWIGLU_OAI
+def _swiglu_oai_run(pkg, be_, shape, form, alpha, limit, xa, xb):
+    """form: split / split_views (operands are views of 3x wider tensors) / single / single_swapped (one tensor of twice the row length)"""
+    ne = list(shape)
+    c = pkg.Context(be_)
+    if form in ("split", "split_views"):
+        if form == "split":
+            a, b = c.new_tensor(F32, *ne), c.new_tensor(F32, *ne)
+            feeds = [(a, xa), (b, xb)]
+        else:
+            feeds, ops = [], []
+            for xv in (xa, xb):
+                wide = c.new_tensor(F32, 3 * ne[0], ne[1], ne[2], ne[3])
+                ops.append(c.view_4d(wide, ne[0], ne[1], ne[2], ne[3], wide.nb[1], wide.nb[2], wide.nb[3], ne[0] * 4))      # the middle third of every row
+                feed = np.full(xv.shape[:-1] + (3 * ne[0],), 1e30, np.float32)
+                feed[..., ne[0]:2 * ne[0]] = xv
+                feeds.append((wide, feed))
+            a, b = ops
+        y = c.swiglu_oai(a, b, alpha, limit)
+    else:
+        a = c.new_tensor(F32, 2 * ne[0], ne[1], ne[2], ne[3])
+        swapped = form == "single_swapped"
+        y = c.swiglu_oai(a, None, alpha, limit, swapped=swapped)
+        feeds = [(a, np.concatenate([xb, xa] if swapped else [xa, xb], axis=-1))]
+    (got,) = _compute(be_, c, [y], feeds)
+    return got.reshape(xa.shape)
+
+
+@pytest.fixture(scope="module")
+def swiglu_oai_inputs():
+    """uniform in +-150 as the reference's test_swiglu_oai, so both clamps act; one pair per shape"""
+    rng = np.random.default_rng(5)
+    return {s: (rng.uniform(-150, 150, s[::-1]).astype(np.float32), rng.uniform(-150, 150, s[::-1]).astype(np.float32)) for s in ((128, 2, 2, 2), (5, 7, 11, 13))}
+
+
+@pytest.mark.parametrize("form", ["split", "split_views", "single", "single_swapped"])
+@pytest.mark.parametrize("alpha,limit", [(0.5, 2.0), (0.5, 7.0), (1.702, 2.0), (1.702, 7.0)])
+@pytest.mark.parametrize("shape", [(128, 2, 2, 2), (5, 7, 11, 13)], ids=["128x2x2x2", "5x7x11x13"])
+def test_swiglu_oai_vs_reference(pkg, be, ref_be, swiglu_oai_inputs, shape, alpha, limit, form):
+    xa, xb = swiglu_oai_inputs[shape]
+    got = _swiglu_oai_run(pkg, be, shape, form, alpha, limit, xa, xb)
+    want = _swiglu_oai_run(pkg, ref_be, shape, form, alpha, limit, xa, xb)
+    x, g = np.minimum(xa.astype(np.float64), limit), np.clip(xb.astype(np.float64), -limit, limit)
+    assert nmse(want, x / (1 + np.exp(-alpha * x)) * (g + 1)) <= 1e-7      # (the fixture: the formula of the issue, operands in the order the form gives them)
+    e = nmse(got, want)
+    print(f"SWIGLU_OAI {shape} {form} alpha {alpha} limit {limit}: NMSE {e:.3e}")
+    assert np.isfinite(got).all() and e <= 1e-7
+
+
+# ------------------------------------------------------------------------------------------------ the gpt-oss expert block
+def _separated_tokens(rng, gate_inp, gate_inp_b, T, n_used, gap=0.25):
+    """T input rows whose biased router logits are well separated around the cut: the n_used + 1 largest of every token at least `gap` apart, so the expert choice
+    does not sit on rounding"""
+    rows = []
+    while len(rows) < T:
+        x = (rng.standard_normal(gate_inp.shape[1]) * 2).astype(np.float32)
+        top = np.sort(gate_inp.astype(np.float64) @ x + gate_inp_b)[::-1][: n_used + 1]
+        if np.min(top[:-1] - top[1:]) >= gap:
+            rows.append(x)
+    return np.stack(rows)
+
+
+def _block_run(pkg, be_, weights, xs):
+    """runs the block once per input in xs on ONE graph (so a backend that captures graphs replays it); -> [(ids [T, n_used], out [T, n_embd])]"""
+    from llama_cpp_omni_amd import gptoss
+    blk = gptoss.GptOssBlock(be_, weights=weights)
+    g, x, N = blk.build(xs[0].shape[0])
+    gr = g.graph()
+    res = []
+    for xv in xs:
+        be_.tensor_set(x, xv)
+        be_.graph_compute(gr)
+        ids = be_.tensor_get(N["argsort"]).copy().reshape(xv.shape[0], -1)[:, : blk.cfg["n_expert_used"]]
+        res.append((ids, be_.tensor_get(N["moe_out"]).copy().reshape(xv.shape[0], -1)))
+    g.free()
+    blk.wctx.free()
+    return res
+
+
+@pytest.fixture(scope="module")
+def gptoss_fixture(pkg, ref_be):
+    """weights, inputs and the reference's results, computed once: tokens 1 and 5, four different inputs each (eager, capture, two replays)"""
+    from llama_cpp_omni_amd import gptoss
+    rng = np.random.default_rng(43)
+    blk = gptoss.GptOssBlock(ref_be, seed=6)
+    weights = blk.weights
+    blk.wctx.free()
+    fx = {"weights": weights}
+    for T in (1, 5):
+        xs = [_separated_tokens(rng, weights["gate_inp"], weights["gate_inp_b"], T, 4) for _ in range(4)]
+        fx[T] = (xs, _block_run(pkg, ref_be, weights, xs))
+    return fx
+
+
+@pytest.mark.parametrize("fusion", [1, 0], ids=["fusion", "no_fusion"])
+@pytest.mark.parametrize("T", [1, 5])
+def test_gptoss_ffn_block_eager_captured_replayed(pkg, be, gptoss_fixture, T, fusion):
+    """the block eager (first submission), captured (second) and replayed (third, fourth), with a NEW router input at every submission so that other experts are
+    chosen: the replayed MUL_MAT_ID and ADD_ID launches must follow the ids they read from device memory"""
+    xs, want = gptoss_fixture[T]
+    assert len({tuple(w[0].ravel()) for w in want}) > 1               # (the fixture: the inputs do choose different experts)
+    keys = ("mmv_id_mxfp4_launches", "add_id_launches", "mmv_id_launches", "argsort_launches", "graph_replays", "graph_captures")
+    be.set_option("fusion", fusion)
+    try:
+        s0 = {k: be.get_stat(k) for k in keys}
+        got = _block_run(pkg, be, gptoss_fixture["weights"], xs)
+        s1 = {k: be.get_stat(k) for k in keys}
+    finally:
+        be.set_option("fusion", 1)
+    worst = 0.0
+    for k, ((gi, go), (wi, wo)) in enumerate(zip(got, want)):
+        assert np.array_equal(gi, wi), (k, gi, wi)
+        e = nmse(go, wo)
+        worst = max(worst, e)
+        assert np.isfinite(go).all() and e <= 5e-4, (k, e)
+    print(f"gpt-oss build_moe_ffn block T {T} fusion {fusion}: worst output NMSE over 4 submissions {worst:.3e}")
+    # four submissions of one graph: eager, capture, two replays -- the launchers ran for the first two only (3 expert nodes, 3 bias nodes, 1 sort each)
+    d = {k: s1[k] - s0[k] for k in keys}
+    assert d["graph_captures"] == 1 and d["graph_replays"] == 2, d
+    assert d["mmv_id_mxfp4_launches"] == 6 and d["add_id_launches"] == 6 and d["argsort_launches"] == 2 and d["mmv_id_launches"] == 0, d
