@@ -163,6 +163,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
     if (!ensure_scratch(c, &c->act_scratch, &c->act_scratch_bytes, graph_act_scratch_need(g)) ||
         !ensure_scratch(c, &c->act_scratch_alt, &c->act_scratch_alt_bytes, any_gemm_cols ? graph_act_scratch_need(g) : 0) ||
         !ensure_scratch(c, &c->w_scratch, &c->w_scratch_bytes, graph_w_scratch_need(g)) ||
+        !ensure_scratch(c, &c->moe_scratch, &c->moe_scratch_bytes, graph_moe_scratch_need(g)) ||
         !ensure_scratch(c, &c->fa_scratch, &c->fa_scratch_bytes, graph_fa_scratch_need(g)) ||
         !ensure_scratch(c, &c->rope_scratch, &c->rope_scratch_bytes, graph_rope_scratch_need(g)) ||
         !ensure_scratch(c, &c->gemm_partial, &c->gemm_partial_bytes, graph_gemm_partial_need(g))) {
@@ -344,6 +345,7 @@ void backend_ctx_release(backend_ctx * c) {
     if (c->act_scratch) (void) hipFree(c->act_scratch);
     if (c->act_scratch_alt) (void) hipFree(c->act_scratch_alt);
     if (c->w_scratch) (void) hipFree(c->w_scratch);
+    if (c->moe_scratch) (void) hipFree(c->moe_scratch);
     if (c->fa_scratch) (void) hipFree(c->fa_scratch);
     if (c->fa_counters) (void) hipFree(c->fa_counters);
     if (c->rope_scratch) (void) hipFree(c->rope_scratch);
@@ -367,6 +369,7 @@ int mi355x_set_option(struct ggml_backend * backend, const char * key, long valu
     if (!strcmp(key, "fp_collide")) { mi::g_fp_collide = value != 0; return 0; }
     if (!strcmp(key, "prefill_q8k")) { mi::prefill_q8k_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: prefill GEMMs of K-quant weights take the Q8_K-quantised activations; 0 = plain f16 rows, the round-4 arithmetic)
     if (!strcmp(key, "mmq_tile")) { mi::mmq_tile_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: the tiled int8-MFMA prefill kernel for Q4_K weights, mmq_tile.hip; 0 = the F16-image GEMM)
+    if (!strcmp(key, "mmq_id")) { mi::mmq_id_set_mode(value != 0); mi::drop_graph_execs(c); return 0; }      // (process-wide: MUL_MAT_ID of K-quant experts from 64 tokens on the expert-grouped int8-MFMA kernel, mmq_id.hip; 0 = the per-pair mat-vec at every token count)
     if (!strcmp(key, "mv2")) { mi::mmv2_enable(value != 0); mi::drop_graph_execs(c); return 0; }       // (process-wide: the LDS-DMA engine form of the decode mat-vec)
     if (!strcmp(key, "kq_staging")) { c->opt_kq_staging = value != 0; mi::drop_graph_execs(c); return 0; }
     if (!strcmp(key, "fattn_gqa")) { mi::fattn_set_gqa(value != 0); mi::drop_graph_execs(c); return 0; }
@@ -410,6 +413,7 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmv_q2k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q2_K);
     if (!strcmp(key, "mmv_q3k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q3_K);
     if (!strcmp(key, "mmv_id_launches"))    return (double) mi::mmv_id_launches();
+    if (!strcmp(key, "mmq_id_launches"))    return (double) mi::mmq_id_launches();
     if (!strcmp(key, "argsort_launches"))   return (double) mi::argsort_launches();
     if (!strcmp(key, "mmv_id_mxfp4_launches")) return (double) mi::mmv_id_mxfp4_launches();
     if (!strcmp(key, "add_id_launches"))    return (double) mi::add_id_launches();

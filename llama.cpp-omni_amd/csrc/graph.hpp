@@ -43,6 +43,8 @@ struct backend_ctx {
     void *  act_scratch_alt = nullptr;  size_t act_scratch_alt_bytes = 0;      // second image buffer: a GEMM that emits the next GEMM's f16 activation image (SWIGLU epilogue) swaps the two
     // scratch for de-quantised weight tiles / f16 copies on the GEMM path
     void *  w_scratch = nullptr;    size_t w_scratch_bytes = 0;
+    // pair list, tile table and tile count of the expert-grouped MUL_MAT_ID (mmq_id.hip): rewritten by every grouped node's first launch
+    void *  moe_scratch = nullptr;  size_t moe_scratch_bytes = 0;
     // mask tile map of the prefill flash-attention kernel
     void *  fa_scratch = nullptr;   size_t fa_scratch_bytes = 0;
     unsigned * fa_counters = nullptr;   // [1024] arrival counters of the sliced one-token attention (zero between launches: the last arriver resets its own)

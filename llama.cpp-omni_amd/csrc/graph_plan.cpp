@@ -290,11 +290,17 @@ mm_route route_mul_mat(const ggml_tensor * n) {
     if (mmq_takes(n)) { r.path = MM_MMQ; return r; }                                  // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
     return r;                                                                         // the type's own mat-vec kernels, on the blocks (w_image only ever with the GEMM)
 }
-// The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]): one path, the per-pair mat-vec at every token count --
-// mmvk.hip for K-quant experts (Q8_K images), mmv_mxfp4.hip for MXFP4 experts (gpt-oss; Q8_0 images, 17-byte blocks: no row or expert alignment condition).
+// The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]).  Two paths:
+//   MM_ID_MMV  the per-pair mat-vec -- mmvk.hip for K-quant experts (Q8_K images), mmv_mxfp4.hip for MXFP4 experts (gpt-oss; Q8_0 images, 17-byte blocks: no row or
+//              expert alignment condition), the latter at every token count;
+//   MM_ID_MMQ  K-quant experts from MMQ_ID_MIN_TOKENS tokens on: the pairs grouped by expert on the device, mmq.hip's int8-MFMA body per (expert, 32 rows, <= 32 columns)
+//              (mmq_id.hip) -- a weight block is read once per 32 columns of its expert instead of once per pair.  Same images, same admission: the path changes
+//              nothing in what supports_op takes.
 // F16 / F32 / BF16 experts and the nine 32-weight block forms of mmvq.hip have no kernel with the id indirection: refused, they stay on the CPU.
+static int g_mmq_id = -1;                                     // option "mmq_id": -1 = MI355X_MMQ_ID decides (default on), 0 off (the cross-check switch), 1 on
+void mmq_id_set_mode(int m) { g_mmq_id = m; }
 mm_id_route route_mul_mat_id(const ggml_tensor * n) {
-    mm_id_route r = { false, ACT_NONE };
+    mm_id_route r = { false, ACT_NONE, MM_ID_MMV };
     const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
     if (!as || !b || !ids) return r;
     const int t = as->type;
@@ -317,6 +323,12 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     const size_t al = t == GGML_TYPE_Q6_K ? 2 : 16;                                                                       // the vector loads' row alignment, as MUL_MAT -- for every expert's rows
     if (as->nb[1] % al != 0 || as->nb[2] % al != 0) return r;
     r.ok = true; r.act = ACT_Q8K;
+    // the grouped kernel: enough tokens, a pair list and an expert histogram of bounded size, the MFMA body's vector-load alignment for expert 0 and (through nb[2]) every
+    // other expert, and its LDS (the columns' block scales: K up to ~70 k)
+    static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
+    if ((g_mmq_id >= 0 ? g_mmq_id : env) && ids->ne[1] >= MMQ_ID_MIN_TOKENS && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS && as->ne[2] <= MMQ_ID_MAX_EXPERTS &&
+        mmq_ok(t, K, as->data, as->nb[1]) && (as->ne[2] == 1 || mmq_ok(t, K, (const char *) as->data + as->nb[2], as->nb[1])) && mmq_id_lds_bytes(K) <= MMQ_ID_LDS_MAX)
+        r.path = MM_ID_MMQ;
     return r;
 }
 bool mm_uses_mmq(const ggml_tensor * n)       { return route_mul_mat(n).path == MM_MMQ; }
@@ -344,6 +356,17 @@ size_t graph_act_scratch_need(const ggml_cgraph * g) {
         const mm_route r = route_mul_mat(n);
         const size_t b = r.path == MM_MMQ_TILE ? mmqt_image_bytes(n->src[1]->ne[0], n->src[1]->ne[1])
                                                : act_image_bytes(r.act, n->src[1]->ne[0]) * (size_t) (n->src[1]->ne[1] * n->src[1]->ne[2] * n->src[1]->ne[3]);
+        if (b > need) need = b;
+    }
+    return need;
+}
+// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip): one grouping per node, the largest node's
+size_t graph_moe_scratch_need(const ggml_cgraph * g) {
+    size_t need = 0;
+    for (int i = 0; i < g->n_nodes; ++i) {
+        const ggml_tensor * n = g->nodes[i];
+        if (n->op != GGML_OP_MUL_MAT_ID || is_empty(n) || route_mul_mat_id(n).path != MM_ID_MMQ) continue;
+        const size_t b = moe_group_bytes(n->src[2]->ne[0] * n->src[2]->ne[1], n->src[0]->ne[2]);
         if (b > need) need = b;
     }
     return need;

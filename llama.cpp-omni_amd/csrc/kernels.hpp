@@ -127,6 +127,16 @@ struct mmq_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_
 struct mmq_args { mmq_mat m[3]; int nmat; const void * act; size_t act_cs; int64_t K; int ncols; };
 bool mmq_ok(int type, int64_t K, const void * W, size_t w_rs);
 void mmq_kquant(const mmq_args & a, hipStream_t st);
+// ---- MUL_MAT_ID on K-quant experts against many tokens (mmq_id.hip): the pairs grouped by expert on the device (k_moe_group: pair list, tile table and tile count into
+// `scratch`, moe_group_bytes), then mmq.hip's body once per (expert, 32-row tile, <= 32-column slice), columns read and results stored through the pair list (k_mmq_id).
+// `m` as for mmv_id_kquant, its experts under mmq_ok's alignment (base, row stride, expert stride).  Nothing reads the ids on the host.
+static const int64_t MMQ_ID_MAX_PAIRS = 1 << 20, MMQ_ID_MAX_EXPERTS = 4096;
+static const size_t  MMQ_ID_LDS_MAX = 64 * 1024;       // column scales of every K block + fold area + the slice's dst offsets (mmq_id_lds_bytes): no launch attribute needed
+struct mmq_id_args { mmv_id_args m; void * scratch; size_t scratch_bytes; };
+size_t moe_group_bytes(int64_t n_pairs, int64_t n_expert);
+size_t mmq_id_lds_bytes(int64_t K);
+void mmq_id_kquant(const mmq_id_args & a, hipStream_t st);
+long mmq_id_launches();                                 // nodes so far (the grouping and the matrix launch count as one; stat "mmq_id_launches")
 // ---- Q4_K weights against a prefill ubatch (> 64 columns) on the int8 matrix cores, tiled (mmq_tile.hip): up to 3 matrices sharing the block-major
 // Q8_K image of the activations (quantize_q8k_tile_image); `resid`: dst = W.x + resid (single matrix, un-split); split-K slabs / deferred reductions as gemm_f16_multi
 struct mmqt_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_t M; const float * resid = nullptr; size_t resid_cs = 0; };
