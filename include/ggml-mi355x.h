@@ -72,7 +72,8 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
  * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
  * "argsort_launches", "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
  * "mmq_id_launches" (MUL_MAT_ID nodes that went through the expert-grouped launchers: the grouping and the matrix launch count as one, and such a node does not
- * touch "mmv_id_launches")
+ * touch "mmv_id_launches"),
+ * "mmq_id_ks" (not a counter: the K split -- waves per tile, 1 / 2 / 4 / 8 -- of the most recent expert-grouped launch, 0 before the first; which k_mmq_id instantiation ran)
  * (all five process-wide; a replayed graph re-runs captured launches without counting them),
  * "shadow_bytes", "shadow_tensors", "prof_mmv_q4k_us", "prof_mmv_q4k_n", "prof_mmv_q4k_bytes", ....
  * Returns -1 if unknown. */

@@ -414,6 +414,7 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmv_q3k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q3_K);
     if (!strcmp(key, "mmv_id_launches"))    return (double) mi::mmv_id_launches();
     if (!strcmp(key, "mmq_id_launches"))    return (double) mi::mmq_id_launches();
+    if (!strcmp(key, "mmq_id_ks"))          return (double) mi::mmq_id_last_ks();
     if (!strcmp(key, "argsort_launches"))   return (double) mi::argsort_launches();
     if (!strcmp(key, "mmv_id_mxfp4_launches")) return (double) mi::mmv_id_mxfp4_launches();
     if (!strcmp(key, "add_id_launches"))    return (double) mi::add_id_launches();

@@ -137,6 +137,7 @@ size_t moe_group_bytes(int64_t n_pairs, int64_t n_expert);
 size_t mmq_id_lds_bytes(int64_t K);
 void mmq_id_kquant(const mmq_id_args & a, hipStream_t st);
 long mmq_id_launches();                                 // nodes so far (the grouping and the matrix launch count as one; stat "mmq_id_launches")
+int  mmq_id_last_ks();                                  // KS (waves splitting K) of the most recent mmq_id_kquant launch, 0 before the first (stat "mmq_id_ks"): read-only
 // ---- Q4_K weights against a prefill ubatch (> 64 columns) on the int8 matrix cores, tiled (mmq_tile.hip): up to 3 matrices sharing the block-major
 // Q8_K image of the activations (quantize_q8k_tile_image); `resid`: dst = W.x + resid (single matrix, un-split); split-K slabs / deferred reductions as gemm_f16_multi
 struct mmqt_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_t M; const float * resid = nullptr; size_t resid_cs = 0; };

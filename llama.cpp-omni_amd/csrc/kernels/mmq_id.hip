@@ -137,6 +137,8 @@ __global__ void __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(2)
 
 static long g_mmq_id_launches = 0;
 long mmq_id_launches() { return g_mmq_id_launches; }
+static int g_mmq_id_ks = 0;                                                            // KS of the most recent launch (0: none yet)
+int mmq_id_last_ks() { return g_mmq_id_ks; }
 
 size_t mmq_id_lds_bytes(int64_t K) { return 32 * sizeof(size_t) + (size_t) (K >> 8) * 32 * 4 + (size_t) 7 * 64 * 16 * 4; }      // at the widest fold (KS = 8)
 
@@ -174,6 +176,7 @@ void mmq_id_kquant(const mmq_id_args & a, hipStream_t st) {
     if (ks == 8) MMQ_ID_GO(8); else if (ks == 4) MMQ_ID_GO(4); else if (ks == 2) MMQ_ID_GO(2); else MMQ_ID_GO(1);
 #undef MMQ_ID_GO
     ++g_mmq_id_launches;
+    g_mmq_id_ks = ks;
 }
 
 } // namespace mi

@@ -6,7 +6,7 @@ Bars: MXFP4 MUL_MAT_ID -- NMSE <= 1e-9, the project's bar for integer mat-vecs a
 same int8 products and power-of-two scales, only the order of the f32 additions over the blocks differs).  ADD_ID -- the reference's bits: one f32 add per element.
 SWIGLU_OAI -- NMSE <= 1e-7, the default of the reference's own harness (test-backend-ops max_nmse_err).  The block -- the selected ids equal, the output inside the
 reference's own bar for MUL_MAT_ID in test-backend-ops (NMSE 5e-4).
-No test feeds an out-of-range id: the kernels clamp them, the reference asserts."""
+No test HERE feeds an out-of-range id (the kernels clamp them, the reference asserts): test_moe_scale_gpu does, on experts that are a view inside a larger tensor."""
 import numpy as np
 import pytest
 

@@ -6,7 +6,8 @@ test_mul_mat_id_vs_reference): only the f32 summation order over the super-block
 of its own weights, its own image and the launch's K split, which the host chooses from the shape alone.  The build_moe_ffn block -- the selected ids equal, the output
 inside the reference's own bar for MUL_MAT_ID in test-backend-ops (NMSE 5e-4).
 The id patterns are written out, so that the tile edges are hit for certain (33 pairs of one expert = a second slice of one column; 32 = exactly one; the last expert;
-empty experts; every pair on one expert = four and more slices of it).  No test feeds an out-of-range id: the kernels clamp them, the reference asserts."""
+empty experts; every pair on one expert = four and more slices of it).  No test HERE feeds an out-of-range id (the kernels clamp them, the reference asserts): the clamp,
+K >= 4096, 128 and more experts and more than 1024 pairs are test_moe_scale_gpu's."""
 import numpy as np
 import pytest
 

@@ -5,7 +5,8 @@ Bars: ARGSORT -- exact equality of the i32 output (distinct values, as the refer
 lower index first).  MUL_MAT_ID -- NMSE <= 1e-9, the project's bar for integer mat-vecs against the same integers (test_mul_mat_vs_oracle_shapes): every output
 is the vec_dot a MUL_MAT column gets, only the f32 summation order over the super-blocks differs.  The block -- the selected ids equal, the output inside the
 reference's own bar for MUL_MAT_ID in test-backend-ops (NMSE 5e-4).
-No test feeds an out-of-range id: the kernel clamps them (mmvk.hip), the reference asserts."""
+No test HERE feeds an out-of-range id (the kernel clamps them, mmvk.hip; the reference asserts), and every sort key is distinct: the clamp, ties and the
+special values are test_moe_scale_gpu's."""
 import numpy as np
 import pytest
 
