@@ -245,11 +245,12 @@ class Model:
         return n
 
     # ---------------------------------------------------------------------------------- graph
-    def build(self, n_tokens, n_kv, n_outputs=None):
+    def build(self, n_tokens, n_kv, n_outputs=None, tap_attn=None):
         """Graph for one ubatch of `n_tokens` new tokens attending to `n_kv` cache cells (llm_build_qwen3).
 
         Inputs (set by the caller before graph_compute): inp_embd [n_embd, n_tokens] f32, inp_pos i32 [n_tokens],
         kq_mask f16 [n_kv, pad(n_tokens, 64)], k_idxs/v_idxs i64 [n_tokens], out_ids i32 [n_outputs].
+        tap_attn ("rows" / "wo", tests only): a SCALE(., 1.0) reader of layer 0's attention rows / wo output, appended to the roots as g.attn_tap.
         """
         c, be = self.cfg, self.be
         E, H, HK, D = c["n_embd"], c["n_head"], c["n_head_kv"], c["head_dim"]
@@ -313,7 +314,11 @@ class Model:
                 if getattr(self, "taps", None) is not None and il == 0:   # debugging aid: keep layer 0's attention intermediates alive
                     self.taps.update(Q=Q, K=K, V=V, kq=kq, kqs=kqs, vt=vt, kqv=kqv, attn=cur)
                     roots += [kq, kqs, vt, kqv, cur]
+            if tap_attn == "rows" and il == 0:                           # test aid, off by default: a second reader keeps layer 0's attention rows materialised
+                g.attn_tap = g.scale(cur, 1.0)
             cur = g.mul_mat(self._w(g, L["attn_output"]), cur)
+            if tap_attn == "wo" and il == 0:                             # ... or its wo output
+                g.attn_tap = g.scale(cur, 1.0)
             if il == n_layer - 1 and "out_ids" in I:
                 cur = g.get_rows(cur, I["out_ids"])
                 inpSA = g.get_rows(inpSA, I["out_ids"])
@@ -329,6 +334,8 @@ class Model:
         if getattr(self, "tap_hidden", False):                         # result_norm as llama_get_embeddings exposes it to the TTS module (omni.cpp:256-270):
             self.hidden_out = g.scale(cur, 1.0)                          # a second reader keeps the rows materialised next to the fused lm-head launch
             roots.append(self.hidden_out)
+        if tap_attn is not None:
+            roots.append(g.attn_tap)
         logits = g.mul_mat(self._w(g, self.output), cur)
         roots.append(logits)
         g.roots = roots
