@@ -198,7 +198,13 @@ class Model:
             self.layers.append(L)
         self.output_norm = w.new_tensor(GGML_TYPE_F32, E)
         self.output = w.new_tensor(types["output"], E, V)
+        # optional per-model frequency factors (rope_freqs.weight of Llama-3.x, llm_build_llama's model.get_rope_factors): [head_dim / 2] f32, src[2] of every ROPE
+        self.rope_freqs = w.new_tensor(GGML_TYPE_F32, D // 2) if c.get("rope_freqs") is not None else None
         w.alloc(usage=GGML_BACKEND_BUFFER_USAGE_WEIGHTS)
+        if self.rope_freqs is not None:
+            ff = np.ascontiguousarray(c["rope_freqs"], np.float32)
+            assert ff.shape == (D // 2,), ff.shape
+            be.tensor_set(self.rope_freqs, ff)
         self.host = {} if host_copy else None
         rng = np.random.default_rng(seed)
         cache = {}
@@ -265,8 +271,11 @@ class Model:
             I["out_ids"] = g.new_tensor(GGML_TYPE_I32, n_outputs)
         kq_scale = 1.0 / math.sqrt(D)
         llama_arch = c.get("arch") == "llama"                          # llm_build_llama (the omni TTS decoder): no q / k norm, RoPE NORM
-        rope = dict(n_dims=D, mode=0 if llama_arch else GGML_ROPE_TYPE_NEOX, n_ctx_orig=c["n_ctx_orig"], freq_base=c["rope_base"], freq_scale=1.0,
-                    ext_factor=0.0, attn_factor=1.0, beta_fast=32.0, beta_slow=1.0)
+        # (the optional rope_* keys: linear / YaRN scaling as llama_context hands it to ggml_rope_ext; absent = plain RoPE)
+        rope = dict(n_dims=D, mode=0 if llama_arch else GGML_ROPE_TYPE_NEOX, n_ctx_orig=c["n_ctx_orig"], freq_base=c["rope_base"], freq_scale=c.get("rope_freq_scale", 1.0),
+                    ext_factor=c.get("rope_ext_factor", 0.0), attn_factor=c.get("rope_attn_factor", 1.0), beta_fast=c.get("rope_beta_fast", 32.0),
+                    beta_slow=c.get("rope_beta_slow", 1.0))
+        rope_ff = self._w(g, self.rope_freqs) if self.rope_freqs is not None else None
         f16 = 2
         inpL = I["inp_embd"]
         n_layer = c["n_layer"]
@@ -281,10 +290,10 @@ class Model:
             V = g.reshape(V, D, HK, n_tokens)
             if not llama_arch:
                 Q = g.mul(g.rms_norm(Q, c["rms_eps"]), self._w(g, L["attn_q_norm"]))
-            Q = g.rope_ext(Q, I["inp_pos"], None, **rope)
+            Q = g.rope_ext(Q, I["inp_pos"], rope_ff, **rope)
             if not llama_arch:
                 K = g.mul(g.rms_norm(K, c["rms_eps"]), self._w(g, L["attn_k_norm"]))
-            K = g.rope_ext(K, I["inp_pos"], None, **rope)
+            K = g.rope_ext(K, I["inp_pos"], rope_ff, **rope)
             # store into the cache (llama_kv_cache::cpy_k / cpy_v, FA layout)
             kc, vc = self._w(g, L["k_cache"]), self._w(g, L["v_cache"])
             roots += [Q, K, V]

@@ -500,3 +500,103 @@ def tile_case(place, qi, ki, kind, alt=False):
     if alt:
         tq, cell = (tq + 32) % nq, (cell + 64) % nkv
     return make_case(128, 128, nq, 2, 1, nkv, 1, kind, 0, 77 + qi + 3 * ki + alt, tile=(tq, cell))
+
+
+# ---------------------------------------------------------------------------------------------------------------- one-token steps through a ONE-layer model
+# The one-token kernels behind the q / k / v pre-stage (k_fattn_one, k_fattn_gs) and the one-token chain without flash-attention (attn_one_sm) are reached only through
+# a layer graph.  The needle directions are the step's own Q after RoPE (g.roots[0]), read from the reference CPU backend on the same weights: a q that the GPU rotates
+# differently loses its needle.  Shared by test_fattn_needle_gpu.py and test_rope_variants_gpu.py; `tag` tells the models of one config apart (a config may hold arrays).
+BAR = 5e-4                                  # the project's and the reference's bar for FLASH_ATTN_EXT, applied per row
+_MODELS = {}
+
+
+def free_models():
+    """the one-layer models live for one test file only (an autouse module fixture of each file calls this)"""
+    for mdl, graphs in _MODELS.values():
+        for g, *_ in graphs.values():
+            g.free()
+        mdl.wctx.free()
+    _MODELS.clear()
+
+
+def model(backend, cfg, types, flash, tag="", n_ctx=4096):
+    from llama_cpp_omni_amd import qwen3
+    key = (id(backend), flash, tag)
+    if key not in _MODELS:
+        _MODELS[key] = (qwen3.Model(backend, cfg, types(cfg), n_ctx=n_ctx, seed=9, flash_attn=flash), {})
+    return _MODELS[key]
+
+
+def step(backend, cfg, types, flash, tap, n_kv, pos, x, caches=None, tag=""):
+    """one decode step at position `pos` over a view of n_kv cells; caches = (K, V) [n_ctx, n_head_kv, head_dim] f16 written first.
+    Returns (Q after RoPE [n_head, head_dim], the tap)"""
+    mdl, graphs = model(backend, cfg, types, flash, tag)
+    if (tap, n_kv) not in graphs:
+        g, I, _ = mdl.build(1, n_kv, tap_attn=tap)
+        graphs[(tap, n_kv)] = (g, I, g.graph(), g.attn_tap)
+    g, I, gr, out = graphs[(tap, n_kv)]
+    if caches is not None:
+        K, V = caches
+        backend.tensor_set(mdl.layers[0]["k_cache"], K)
+        backend.tensor_set(mdl.layers[0]["v_cache"], V if not mdl.v_trans else np.ascontiguousarray(V.reshape(V.shape[0], -1).T))
+    mdl.set_inputs(I, x, pos, n_kv)
+    backend.graph_compute(gr)
+    return backend.tensor_get(g.roots[0]).astype(np.float64).reshape(cfg["n_head"], cfg["head_dim"]), backend.tensor_get(out).astype(np.float64).ravel()
+
+
+def k_cache_row(backend, cfg, types, flash, cell, tag=""):
+    """layer 0's K cache row of `cell` as the last step left it: [n_head_kv, head_dim] f16"""
+    mdl, _ = model(backend, cfg, types, flash, tag)
+    nb = cfg["n_head_kv"] * cfg["head_dim"] * 2
+    return backend.tensor_get(mdl.layers[0]["k_cache"], np.float16, cell * nb, nb).copy().reshape(cfg["n_head_kv"], cfg["head_dim"])
+
+
+def needle_caches(rng, Q, cells, pos, n_kv, n_ctx=4096, n_head_kv=8):
+    """K / V caches [n_ctx, n_head_kv, D] f16: head h's needle -- its own query direction, score L -- in cell cells[h] of its KV head, a decoy of every head in the first
+    cells behind the causal edge and in the last cell of the view"""
+    H, D = Q.shape
+    gq = H // n_head_kv
+    K = (0.05 * rng.standard_normal((n_ctx, n_head_kv, D))).astype(np.float32)
+    V = rng.standard_normal((n_ctx, n_head_kv, D)).astype(np.float16)
+    scale = 1.0 / np.sqrt(float(D))
+    for h in range(H):
+        u = Q[h] / (scale * (Q[h] ** 2).sum())                       # scale * q . u = 1
+        K[cells[h], h // gq] += L * u
+        for d in {pos + 1, n_kv - 1} - {pos}:
+            K[d, h // gq] += 2 * L * u
+    return K.astype(np.float16), V
+
+
+def slice_edges(width, pos):
+    """the cells at the edges of `width`-row slices below the new token's cell, the first cells and the newest ones"""
+    e = [pos - 1, pos - 2, 0, 1]
+    for m in range(width, pos, width):
+        e += [m - 1, m, m + 1]
+    return [c for c in dict.fromkeys(e) if 0 <= c < pos]
+
+
+def head_rows(tag, rows_gpu, rows_ref, V, cells):
+    """every head's attention row [n_head, D] against its needle's V row and against the reference backend's row; returns the worst of each"""
+    H = len(cells)
+    gq = H // V.shape[1]
+    worst = (0.0, 0.0)
+    for h in range(H):
+        want = V[cells[h], h // gq].astype(np.float64)
+        e_v = float(row_nmse(rows_gpu[h][None], want[None])[0]); e_r = float(row_nmse(rows_gpu[h][None], rows_ref[h][None])[0])
+        e_rv = float(row_nmse(rows_ref[h][None], want[None])[0])
+        worst = (max(worst[0], e_v), max(worst[1], e_r))
+        assert e_rv < 1e-8, (tag, "the reference's row is not its needle's V row", h, cells[h], e_rv)
+        assert e_v < BAR and e_r < BAR, (tag, h, cells[h], e_v, e_r)
+    print(f"{tag}: worst head row vs its needle's V row {worst[0]:.3e}, vs the reference backend {worst[1]:.3e}")
+    return worst
+
+
+def launches(be, cfg, types, flash, n_kv, pos, x, caches, option=None, tag=""):
+    """kernels_last_graph of the step, eager (setting an option drops the captured graphs), with `option` switched off"""
+    be.set_option(option or "fattn_gqa", 0 if option else 1)
+    try:
+        _, rows = step(be, cfg, types, flash, "rows", n_kv, pos, x, caches, tag)
+        return int(be.get_stat("kernels_last_graph")), rows
+    finally:
+        if option:
+            be.set_option(option, 1)

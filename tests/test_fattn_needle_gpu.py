@@ -20,7 +20,7 @@ from test_gpu_parity import _attn_f64
 
 pytestmark = pytest.mark.gpu
 
-BAR = 5e-4
+BAR = fn.BAR                                # 5e-4
 
 # name: (option fattn_gqa, option fattn_dma (-1: default), kernels_last_graph with a mask, ring launches)
 LAUNCH = {
@@ -244,93 +244,33 @@ def test_soft_max_attention_chain_needle_rows(pkg, be, request, cid):
 # ---- the one-token kernels behind the q / k / v pre-stage (k_fattn_one, k_fattn_gs) and the one-token chain without flash-attention (attn_one_sm) are reached only
 # through a layer graph: ONE layer at Qwen3-8B's attention widths (n_embd 4096, 32 / 8 heads of 128: what fattn_gs_ok and the folding wo launch ask for), the smallest
 # ffn and vocabulary the K-quant rows take.  The needle directions are the step's own Q after RoPE (g.roots[0]), read from the reference CPU backend on the same weights.
+# (the step helpers live in fattn_needle.py: test_rope_variants_gpu.py runs the same steps with other rotations)
 def _cfg1():
     import test_round6_gpu as r6
     return dict(r6.CFG, n_layer=1, n_ff=256, n_vocab=256)
 
 
-_MODELS = {}
+def _types(cfg):
+    from llama_cpp_omni_amd import qwen3
+    return qwen3.q4_k_m_types(cfg)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _free_models():
     """the one-layer models live for this file only"""
     yield
-    for mdl, graphs in _MODELS.values():
-        for g, *_ in graphs.values():
-            g.free()
-        mdl.wctx.free()
-    _MODELS.clear()
-
-
-def _model(pkg, backend, flash, n_ctx=4096):
-    from llama_cpp_omni_amd import qwen3
-    key = (id(backend), flash)
-    if key not in _MODELS:
-        cfg = _cfg1()
-        _MODELS[key] = (qwen3.Model(backend, cfg, qwen3.q4_k_m_types(cfg), n_ctx=n_ctx, seed=9, flash_attn=flash), {})
-    return _MODELS[key]
+    fn.free_models()
 
 
 def _step(pkg, backend, flash, tap, n_kv, pos, x, caches=None):
-    """one decode step at position `pos` over a view of n_kv cells; caches = (K, V) [n_ctx, 8, 128] f16 written first.  Returns (Q after RoPE [32, 128], the tap)"""
-    mdl, graphs = _model(pkg, backend, flash)
-    if (tap, n_kv) not in graphs:
-        g, I, _ = mdl.build(1, n_kv, tap_attn=tap)
-        graphs[(tap, n_kv)] = (g, I, g.graph(), g.attn_tap)
-    g, I, gr, out = graphs[(tap, n_kv)]
-    if caches is not None:
-        K, V = caches
-        backend.tensor_set(mdl.layers[0]["k_cache"], K)
-        backend.tensor_set(mdl.layers[0]["v_cache"], V if not mdl.v_trans else np.ascontiguousarray(V.reshape(V.shape[0], -1).T))
-    mdl.set_inputs(I, x, pos, n_kv)
-    backend.graph_compute(gr)
-    return backend.tensor_get(g.roots[0]).astype(np.float64).reshape(32, 128), backend.tensor_get(out).astype(np.float64).ravel()
-
-
-def _needle_caches(rng, Q, cells, pos, n_kv, n_ctx=4096):
-    """K / V caches [n_ctx, 8, 128] f16: head h's needle -- its own query direction, score L -- in cell cells[h] of KV head h // 4, a decoy of every head in the first
-    cells behind the causal edge and in the last cell of the view"""
-    K = (0.05 * rng.standard_normal((n_ctx, 8, 128))).astype(np.float32)
-    V = rng.standard_normal((n_ctx, 8, 128)).astype(np.float16)
-    scale = 1.0 / np.sqrt(128.0)
-    for h in range(32):
-        u = Q[h] / (scale * (Q[h] ** 2).sum())                       # scale * q . u = 1
-        K[cells[h], h // 4] += fn.L * u
-        for d in {pos + 1, n_kv - 1} - {pos}:
-            K[d, h // 4] += 2 * fn.L * u
-    return K.astype(np.float16), V
-
-
-def _slice_edges(width, pos):
-    """the cells at the edges of `width`-row slices below the new token's cell, the first cells and the newest ones"""
-    e = [pos - 1, pos - 2, 0, 1]
-    for m in range(width, pos, width):
-        e += [m - 1, m, m + 1]
-    return [c for c in dict.fromkeys(e) if 0 <= c < pos]
-
-
-def _head_rows(tag, rows_gpu, rows_ref, V, cells):
-    worst = (0.0, 0.0)
-    for h in range(32):
-        want = V[cells[h], h // 4].astype(np.float64)
-        e_v = float(fn.row_nmse(rows_gpu[h][None], want[None])[0]); e_r = float(fn.row_nmse(rows_gpu[h][None], rows_ref[h][None])[0])
-        e_rv = float(fn.row_nmse(rows_ref[h][None], want[None])[0])
-        worst = (max(worst[0], e_v), max(worst[1], e_r))
-        assert e_rv < 1e-8, (tag, "the reference's row is not its needle's V row", h, cells[h], e_rv)
-        assert e_v < BAR and e_r < BAR, (tag, h, cells[h], e_v, e_r)
-    print(f"{tag}: worst head row vs its needle's V row {worst[0]:.3e}, vs the reference backend {worst[1]:.3e}")
+    return fn.step(backend, _cfg1(), _types, flash, tap, n_kv, pos, x, caches)
 
 
 def _launches(pkg, be, flash, n_kv, pos, x, caches, option=None):
-    """kernels_last_graph of the step, eager (setting an option drops the captured graphs), with `option` switched off"""
-    be.set_option(option or "fattn_gqa", 0 if option else 1)
-    try:
-        _, rows = _step(pkg, be, flash, "rows", n_kv, pos, x, caches)
-        return int(be.get_stat("kernels_last_graph")), rows
-    finally:
-        if option:
-            be.set_option(option, 1)
+    return fn.launches(be, _cfg1(), _types, flash, n_kv, pos, x, caches, option)
+
+
+_needle_caches, _slice_edges, _head_rows = fn.needle_caches, fn.slice_edges, fn.head_rows
 
 
 # kernels_last_graph of the one-layer step with the rows tapped, as the executor reports it: (the one-token kernel, option fattn_one 0).  k_fattn_one reads the token's
