@@ -188,14 +188,20 @@ struct mm_route {
     int64_t  k_head_sized;   // what graph_gemm_partial_need reserves split-K scratch for: k_head's shape rule alone, on any path behind the F16 GEMM's
 };
 mm_route route_mul_mat(const ggml_tensor * n);
-// ... and a MUL_MAT_ID node: admitted or not (supports_op), the image of b's columns its path reads (both paths of a K-quant node read ACT_Q8K) and the path: the
-// per-pair mat-vec, or from MMQ_ID_MIN_TOKENS tokens on the expert-grouped int8-MFMA kernel (scratch sizing, the executor's MUL_MAT_ID case)
+// ... and a MUL_MAT_ID node: admitted or not (supports_op), the image of b's columns its path reads (both paths of a K-quant node read ACT_Q8K, both of an MXFP4 node
+// ACT_Q80) and the path: the per-pair mat-vec, or from MMQ_ID_MIN_TOKENS (K-quants) / mmq_id_mxfp4_min_tokens() (MXFP4) tokens on the expert-grouped int8-MFMA kernel
+// of the type (scratch sizing, the executor's MUL_MAT_ID case)
 enum mm_id_path { MM_ID_MMV, MM_ID_MMQ };
 struct mm_id_route { bool ok; act_kind act; mm_id_path path; };
 mm_id_route route_mul_mat_id(const ggml_tensor * n);
 // the token count from which K-quant experts take the grouped kernel.  Above 33: up to there one mmv_id launch per node is what the per-pair tests count.
 static const int64_t MMQ_ID_MIN_TOKENS = 64;
 static_assert(MMQ_ID_MIN_TOKENS > 33, "the per-pair mat-vec keeps every token count up to 33");
+// ... and MXFP4 experts theirs (mmq_id_mxfp4.hip).  Above 64: the per-pair MXFP4 tests count one mmv_id_mxfp4 launch per node up to 64 tokens.  MI355X_MMQ_ID_MXFP4_MIN_TOKENS
+// (read once, floor 65) moves it for measurements: mmq_id_mxfp4_min_tokens()
+static const int64_t MMQ_ID_MXFP4_MIN_TOKENS = 128;
+static_assert(MMQ_ID_MXFP4_MIN_TOKENS > 64, "the per-pair MXFP4 mat-vec keeps every token count up to 64");
+int64_t mmq_id_mxfp4_min_tokens();
 void mmq_id_set_mode(int m);                            // option "mmq_id": 0 = every node on the per-pair kernel
 // one row per admitted weight type (null: none; BF16 has a path of its own): the image its mat-vec kernels read, their launcher (up to 8 columns) and profile class
 struct mmv_row { int type; act_kind act; void (*launch)(const mmv_args &, hipStream_t); const char * cls; };

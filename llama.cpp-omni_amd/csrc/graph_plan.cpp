@@ -292,13 +292,18 @@ mm_route route_mul_mat(const ggml_tensor * n) {
 }
 // The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]).  Two paths:
 //   MM_ID_MMV  the per-pair mat-vec -- mmvk.hip for K-quant experts (Q8_K images), mmv_mxfp4.hip for MXFP4 experts (gpt-oss; Q8_0 images, 17-byte blocks: no row or
-//              expert alignment condition), the latter at every token count;
+//              expert alignment condition);
 //   MM_ID_MMQ  K-quant experts from MMQ_ID_MIN_TOKENS tokens on: the pairs grouped by expert on the device, mmq.hip's int8-MFMA body per (expert, 32 rows, <= 32 columns)
-//              (mmq_id.hip) -- a weight block is read once per 32 columns of its expert instead of once per pair.  Same images, same admission: the path changes
+//              (mmq_id.hip) -- a weight block is read once per 32 columns of its expert instead of once per pair.  MXFP4 experts from mmq_id_mxfp4_min_tokens() tokens
+//              on: the same grouping, one int8 MFMA per 17-byte block (mmq_id_mxfp4.hip), no alignment condition.  Same images, same admission: the path changes
 //              nothing in what supports_op takes.
 // F16 / F32 / BF16 experts and the nine 32-weight block forms of mmvq.hip have no kernel with the id indirection: refused, they stay on the CPU.
 static int g_mmq_id = -1;                                     // option "mmq_id": -1 = MI355X_MMQ_ID decides (default on), 0 off (the cross-check switch), 1 on
 void mmq_id_set_mode(int m) { g_mmq_id = m; }
+int64_t mmq_id_mxfp4_min_tokens() {
+    static const int64_t v = [] { const char * e = getenv("MI355X_MMQ_ID_MXFP4_MIN_TOKENS"); const int64_t n = e ? atoll(e) : MMQ_ID_MXFP4_MIN_TOKENS; return n < 65 ? (int64_t) 65 : n; }();
+    return v;
+}
 mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     mm_id_route r = { false, ACT_NONE, MM_ID_MMV };
     const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
@@ -316,6 +321,11 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
         if (K < 32 || K % 32 != 0 || K > INT32_MAX || q80_image_bytes(K) > (size_t) 152 * 1024) return r;                 // one column's Q8_0 image in LDS
         if (as->nb[1] < row_size(t, K)) return r;
         r.ok = true; r.act = ACT_Q80;
+        // the grouped kernel: enough tokens, a pair list and an expert histogram of bounded size, its LDS (the columns' block scales: K up to ~9 k)
+        static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
+        if ((g_mmq_id >= 0 ? g_mmq_id : env) && ids->ne[1] >= mmq_id_mxfp4_min_tokens() && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS && as->ne[2] <= MMQ_ID_MAX_EXPERTS &&
+            mmq_id_mxfp4_lds_bytes(K) <= MMQ_ID_LDS_MAX)
+            r.path = MM_ID_MMQ;
         return r;
     }
     if (K % 256 != 0 || K > INT32_MAX || q8k_image_bytes(K) > (size_t) 152 * 1024) return r;                              // one column's image in LDS
@@ -360,7 +370,7 @@ size_t graph_act_scratch_need(const ggml_cgraph * g) {
     }
     return need;
 }
-// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip): one grouping per node, the largest node's
+// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip; K-quant and MXFP4 nodes alike): one grouping per node, the largest node's
 size_t graph_moe_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;
     for (int i = 0; i < g->n_nodes; ++i) {

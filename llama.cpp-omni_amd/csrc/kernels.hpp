@@ -136,8 +136,20 @@ struct mmq_id_args { mmv_id_args m; void * scratch; size_t scratch_bytes; };
 size_t moe_group_bytes(int64_t n_pairs, int64_t n_expert);
 size_t mmq_id_lds_bytes(int64_t K);
 void mmq_id_kquant(const mmq_id_args & a, hipStream_t st);
-long mmq_id_launches();                                 // nodes so far (the grouping and the matrix launch count as one; stat "mmq_id_launches")
+long mmq_id_launches();                                 // K-quant nodes so far (the grouping and the matrix launch count as one; stat "mmq_id_launches")
 int  mmq_id_last_ks();                                  // KS (waves splitting K) of the most recent mmq_id_kquant launch, 0 before the first (stat "mmq_id_ks"): read-only
+// the grouping on its own, for the matrix kernels of both files: one launch of k_moe_group into `scratch` (moe_group_bytes(n_ids * n_tokens, n_expert) bytes; the caller
+// checks the counts against MMQ_ID_MAX_*), the device pointers of what it writes.  Every id is clamped into [0, n_expert) there: the tile table names valid experts only.
+struct moe_tile { int expert, first, ncols; };          // one non-empty (expert, <= 32-column slice): the expert, the slice's first position in the pair list, its column count
+struct moe_group_out { const int * count; const moe_tile * tiles; const int * list; };
+int64_t moe_tile_bound(int64_t n_pairs, int64_t n_expert);      // the host-side bound on the tile count: the matrix kernels' grid y
+moe_group_out moe_group_launch(const mmv_id_args & m, void * scratch, hipStream_t st);
+// ---- the same on MXFP4 experts (mmq_id_mxfp4.hip; gpt-oss prefill): k_moe_group's tables, then one int8 MFMA per 32-weight block and (32 rows, <= 32 columns) against
+// the Q8_0 images -- ggml_vec_dot_mxfp4_q8_0's integers and product order, as mmv_id_mxfp4.  `m` as for mmv_id_mxfp4: 17-byte blocks, no alignment condition.
+size_t mmq_id_mxfp4_lds_bytes(int64_t K);               // the slice's dst offsets + the columns' block scales + the widest fold: <= MMQ_ID_LDS_MAX is the route's condition
+void mmq_id_mxfp4(const mmq_id_args & a, hipStream_t st);
+long mmq_id_mxfp4_launches();                           // MXFP4 nodes so far (grouping + matrix launch = one; stat "mmq_id_mxfp4_launches")
+int  mmq_id_mxfp4_last_ks();                            // KS of the most recent mmq_id_mxfp4 launch, 0 before the first (stat "mmq_id_mxfp4_ks"): read-only
 // ---- Q4_K weights against a prefill ubatch (> 64 columns) on the int8 matrix cores, tiled (mmq_tile.hip): up to 3 matrices sharing the block-major
 // Q8_K image of the activations (quantize_q8k_tile_image); `resid`: dst = W.x + resid (single matrix, un-split); split-K slabs / deferred reductions as gemm_f16_multi
 struct mmqt_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_t M; const float * resid = nullptr; size_t resid_cs = 0; };

@@ -19,7 +19,7 @@
 
 namespace mi {
 
-struct moe_tile { int expert, first, ncols; };
+// (moe_tile, one entry of the tile table, and moe_group_out, where a grouping lies in the scratch: kernels.hpp -- mmq_id_mxfp4.hip reads the same tables)
 static constexpr size_t MOE_HDR = 16;                                                  // the tile count, padded so that the table behind it is 16-byte aligned
 
 int64_t moe_tile_bound(int64_t n_pairs, int64_t n_expert) { return (n_pairs < n_expert ? n_pairs : n_expert) + n_pairs / 32; }
@@ -142,6 +142,17 @@ int mmq_id_last_ks() { return g_mmq_id_ks; }
 
 size_t mmq_id_lds_bytes(int64_t K) { return 32 * sizeof(size_t) + (size_t) (K >> 8) * 32 * 4 + (size_t) 7 * 64 * 16 * 4; }      // at the widest fold (KS = 8)
 
+// the grouping of one node into its scratch (moe_group_bytes; the caller has checked the pair and expert counts against MMQ_ID_MAX_* and the scratch size)
+moe_group_out moe_group_launch(const mmv_id_args & m, void * scratch, hipStream_t st) {
+    const int64_t n_pairs = m.n_ids * m.n_tokens, bound = moe_tile_bound(n_pairs, m.n_expert);
+    moe_group_dev g;
+    g.ids = (const char *) m.ids; g.ids_nb0 = m.ids_nb0; g.ids_nb1 = m.ids_nb1;
+    g.n_ids = (int) m.n_ids; g.n_pairs = (int) n_pairs; g.n_expert = (int) m.n_expert;
+    g.count = (int *) scratch; g.tiles = (moe_tile *) ((char *) scratch + MOE_HDR); g.list = (int *) ((char *) scratch + MOE_HDR + (size_t) bound * sizeof(moe_tile));
+    k_moe_group<<<dim3(1), dim3(GROUP_THREADS), ((size_t) m.n_expert * 2 + GROUP_THREADS * 2) * 4, st>>>(g);
+    return { g.count, g.tiles, g.list };
+}
+
 void mmq_id_kquant(const mmq_id_args & a, hipStream_t st) {
     const mmv_id_args & m = a.m;
     if (m.nrows == 0 || m.n_ids == 0 || m.n_tokens == 0) return;
@@ -152,11 +163,7 @@ void mmq_id_kquant(const mmq_id_args & a, hipStream_t st) {
                 (long long) m.n_tokens, (long long) m.n_expert); abort();
     }
     const int64_t bound = moe_tile_bound(n_pairs, m.n_expert);                          // <= 4096 + 2^15: inside grid y
-    moe_group_dev g;
-    g.ids = (const char *) m.ids; g.ids_nb0 = m.ids_nb0; g.ids_nb1 = m.ids_nb1;
-    g.n_ids = (int) m.n_ids; g.n_pairs = (int) n_pairs; g.n_expert = (int) m.n_expert;
-    g.count = (int *) a.scratch; g.tiles = (moe_tile *) ((char *) a.scratch + MOE_HDR); g.list = (int *) ((char *) a.scratch + MOE_HDR + (size_t) bound * sizeof(moe_tile));
-    k_moe_group<<<dim3(1), dim3(GROUP_THREADS), ((size_t) m.n_expert * 2 + GROUP_THREADS * 2) * 4, st>>>(g);
+    const moe_group_out g = moe_group_launch(m, a.scratch, st);
 
     mmq_id_dev d;
     d.as = (const char *) m.as; d.as_nb1 = m.as_nb1; d.as_nb2 = m.as_nb2;
