@@ -59,14 +59,15 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * "prefill_q8k" (0 default / 1: the prefill GEMMs of K-quant weights take the Q8_K-QUANTISED activations -- the reference CPU backend's vec_dot_type
  * arithmetic, ggml-cpu.c:1245-1268 -- instead of plain f16 rows; process-wide), "mmq_tile" (0 default / 1: Q4_K weights x more than 64 columns on the int8
  * matrix cores from the blocks, csrc/kernels/mmq_tile.hip: the oracle's exact integer sums, slower than the F16-image GEMM; process-wide),
- * "mmq_id" (1 default / 0: MUL_MAT_ID of Q4_K / Q5_K / Q6_K experts from 64 tokens on, and of MXFP4 experts from 128 tokens on, runs on the expert-grouped int8-MFMA
- * kernels, csrc/kernels/mmq_id.hip / mmq_id_mxfp4.hip -- the pairs sorted by expert on the device, one tile per (expert, 32 rows, <= 32 columns); 0 sends every node
+ * "mmq_id" (1 default / 0: MUL_MAT_ID of Q4_K / Q5_K / Q6_K experts from 64 tokens on, of MXFP4 experts from 128 and of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts from 65 tokens on, runs on the
+ * expert-grouped int8-MFMA kernels, csrc/kernels/mmq_id.hip / mmq_id_mxfp4.hip / mmq_id_blocks.hip -- the pairs sorted by expert on the device, one tile per (expert, 32 rows, <= 32 columns); 0 sends every node
  * to the per-pair mat-vec: the cross-check switch; process-wide),
  * "mv1", "mv2", "fattn_one", "kq_staging", "batch_uploads" (cross-check switches of the decode kernels),
  * "reset_stats".  Returns 0 on success, -1 for an unknown key.
  * Environment switches read once per process (measurement / cross-check only): MI355X_GRAPHS=0, MI355X_NO_CONV_FUSE, MI355X_NO_CONCAT_TAIL, MI355X_NO_ATTN_F32,
  * MI355X_NO_GEMM_F32_T16, MI355X_NO_NORM_FUSE, MI355X_NO_GATE_NORM, MI355X_NO_EW_CHAIN, MI355X_NO_CONT_SINK (each turns one graph matcher / kernel choice off);
- * MI355X_MMQ_ID=0 (option "mmq_id" off), MI355X_MMQ_ID_MXFP4_MIN_TOKENS=n (the token count from which MXFP4 experts are grouped: default 128, floor 65);
+ * MI355X_MMQ_ID=0 (option "mmq_id" off), MI355X_MMQ_ID_MXFP4_MIN_TOKENS=n (the token count from which MXFP4 experts are grouped: default 128, floor 65),
+ * MI355X_MMQ_ID_BLOCKS_MIN_TOKENS=n (the same for Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts: default 65, floor 65);
  * MI355X_LOG_STATS, MI355X_GRAPH_GPU_TIME, MI355X_LAUNCH_LOG=file, MI355X_GRAPH_SLICE="nodes:lo:hi,..." (instrumentation, see tools/t2w_slices.sh). */
 GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const char * key, long value);
 /* counters: "graph_replays", "graph_captures", "eager_graphs", "kernels_last_graph", "mmq_tile_launches",
@@ -76,8 +77,11 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
  * "mmq_id_launches" (MUL_MAT_ID nodes of K-quant experts that went through the expert-grouped launchers: the grouping and the matrix launch count as one, and such a
  * node does not touch "mmv_id_launches"), "mmq_id_mxfp4_launches" (the same for MXFP4 experts, counted apart; such a node does not touch "mmv_id_mxfp4_launches"),
  * "mmq_id_mxfp4_ks" (as "mmq_id_ks", for the most recent grouped MXFP4 launch),
+ * "mmv_id_blocks_launches" (MUL_MAT_ID launches on Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL / IQ4_XS / Q2_K / Q3_K experts, counted apart from "mmv_id_launches"),
+ * "mmq_id_blocks_launches" (grouped nodes of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts, counted apart; such a node does not touch "mmv_id_blocks_launches"),
+ * "mmq_id_blocks_ks" (as "mmq_id_ks", for the most recent of those),
  * "mmq_id_ks" (not a counter: the K split -- waves per tile, 1 / 2 / 4 / 8 -- of the most recent expert-grouped launch, 0 before the first; which k_mmq_id instantiation ran)
- * (all seven process-wide; a replayed graph re-runs captured launches without counting them),
+ * (all of them process-wide; a replayed graph re-runs captured launches without counting them),
  * "shadow_bytes", "shadow_tensors", "prof_mmv_q4k_us", "prof_mmv_q4k_n", "prof_mmv_q4k_bytes", ....
  * Returns -1 if unknown. */
 GGML_MI355X_API double mi355x_get_stat(struct ggml_backend * backend, const char * key);

@@ -189,8 +189,8 @@ struct mm_route {
 };
 mm_route route_mul_mat(const ggml_tensor * n);
 // ... and a MUL_MAT_ID node: admitted or not (supports_op), the image of b's columns its path reads (both paths of a K-quant node read ACT_Q8K, both of an MXFP4 node
-// ACT_Q80) and the path: the per-pair mat-vec, or from MMQ_ID_MIN_TOKENS (K-quants) / mmq_id_mxfp4_min_tokens() (MXFP4) tokens on the expert-grouped int8-MFMA kernel
-// of the type (scratch sizing, the executor's MUL_MAT_ID case)
+// ACT_Q80, a block-form node the image of its dense mat-vec) and the path: the per-pair mat-vec, or from MMQ_ID_MIN_TOKENS (K-quants) / mmq_id_mxfp4_min_tokens() (MXFP4) /
+// mmq_id_blocks_min_tokens() (Q8_0, Q4_0, Q5_0, IQ4_NL) tokens on the expert-grouped int8-MFMA kernel of the type (scratch sizing, the executor's MUL_MAT_ID case)
 enum mm_id_path { MM_ID_MMV, MM_ID_MMQ };
 struct mm_id_route { bool ok; act_kind act; mm_id_path path; };
 mm_id_route route_mul_mat_id(const ggml_tensor * n);
@@ -202,6 +202,12 @@ static_assert(MMQ_ID_MIN_TOKENS > 33, "the per-pair mat-vec keeps every token co
 static const int64_t MMQ_ID_MXFP4_MIN_TOKENS = 128;
 static_assert(MMQ_ID_MXFP4_MIN_TOKENS > 64, "the per-pair MXFP4 mat-vec keeps every token count up to 64");
 int64_t mmq_id_mxfp4_min_tokens();
+// ... and Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts theirs (mmq_id_blocks.hip).  Above 64: the per-pair tests keep their path.  65 is the measured value: at the Qwen3-30B-A3B
+// and DeepSeek-V2-Lite expert shapes the grouped kernel is level with the per-pair one (Q4_0, 1.00 x) or ahead (up to 2.6 x) at 65 tokens already and ahead from there
+// on, for all four forms (profiles/moe_blocks_crossover.txt).  MI355X_MMQ_ID_BLOCKS_MIN_TOKENS (read once, floor 65) moves it for measurements: mmq_id_blocks_min_tokens()
+static const int64_t MMQ_ID_BLOCKS_MIN_TOKENS = 65;
+static_assert(MMQ_ID_BLOCKS_MIN_TOKENS > 64, "the per-pair block-form mat-vec keeps every token count up to 64");
+int64_t mmq_id_blocks_min_tokens();
 void mmq_id_set_mode(int m);                            // option "mmq_id": 0 = every node on the per-pair kernel
 // one row per admitted weight type (null: none; BF16 has a path of its own): the image its mat-vec kernels read, their launcher (up to 8 columns) and profile class
 struct mmv_row { int type; act_kind act; void (*launch)(const mmv_args &, hipStream_t); const char * cls; };

@@ -297,11 +297,21 @@ mm_route route_mul_mat(const ggml_tensor * n) {
 //              (mmq_id.hip) -- a weight block is read once per 32 columns of its expert instead of once per pair.  MXFP4 experts from mmq_id_mxfp4_min_tokens() tokens
 //              on: the same grouping, one int8 MFMA per 17-byte block (mmq_id_mxfp4.hip), no alignment condition.  Same images, same admission: the path changes
 //              nothing in what supports_op takes.
-// F16 / F32 / BF16 experts and the nine 32-weight block forms of mmvq.hip have no kernel with the id indirection: refused, they stay on the CPU.
+// Experts of the nine block forms of mmvq.hip (Q8_0, Q4_0/1, Q5_0/1, IQ4_NL/XS, Q2_K, Q3_K):
+//   MM_ID_MMV  the dense frame at one column behind the id indirection (mmvq.hip k_mmv_blocks_id), on the image the form's dense mat-vec reads (Q8_0 / Q8_1 / Q8_K);
+//              row and expert strides under the form's alignment, as supports_op states for MUL_MAT (4 bytes and a 4-byte-aligned base for Q4_1 / Q5_1 / Q2_K, 2 bytes
+//              for the rest);
+//   MM_ID_MMQ  Q8_0 / Q4_0 / Q5_0 / IQ4_NL (a 32-weight block against the Q8_0 image, no min term) from mmq_id_blocks_min_tokens() tokens on: the grouping, then one int8
+//              MFMA per block (mmq_id_blocks.hip).  Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_XS experts stay per-pair at every token count.
+// F16 / F32 / BF16 experts have no kernel with the id indirection: refused, they stay on the CPU.
 static int g_mmq_id = -1;                                     // option "mmq_id": -1 = MI355X_MMQ_ID decides (default on), 0 off (the cross-check switch), 1 on
 void mmq_id_set_mode(int m) { g_mmq_id = m; }
 int64_t mmq_id_mxfp4_min_tokens() {
     static const int64_t v = [] { const char * e = getenv("MI355X_MMQ_ID_MXFP4_MIN_TOKENS"); const int64_t n = e ? atoll(e) : MMQ_ID_MXFP4_MIN_TOKENS; return n < 65 ? (int64_t) 65 : n; }();
+    return v;
+}
+int64_t mmq_id_blocks_min_tokens() {
+    static const int64_t v = [] { const char * e = getenv("MI355X_MMQ_ID_BLOCKS_MIN_TOKENS"); const int64_t n = e ? atoll(e) : MMQ_ID_BLOCKS_MIN_TOKENS; return n < 65 ? (int64_t) 65 : n; }();
     return v;
 }
 mm_id_route route_mul_mat_id(const ggml_tensor * n) {
@@ -309,7 +319,9 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
     if (!as || !b || !ids) return r;
     const int t = as->type;
-    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K && t != GGML_TYPE_MXFP4) return r;
+    const bool blocks = t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_IQ4_NL ||
+                        t == GGML_TYPE_IQ4_XS || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K;
+    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K && t != GGML_TYPE_MXFP4 && !blocks) return r;
     if (b->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32) return r;
     if (as->nb[0] != type_size(t) || b->nb[0] != 4 || n->nb[0] != 4 || ids->nb[0] % 4 != 0 || ids->nb[1] % 4 != 0 || b->nb[1] % 4 != 0) return r;
     if (as->ne[3] != 1 || b->ne[3] != 1 || ids->ne[2] != 1 || ids->ne[3] != 1 || n->ne[3] != 1) return r;                 // the asserts of ggml_mul_mat_id (ggml.c:3088-3096)
@@ -325,6 +337,20 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
         static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
         if ((g_mmq_id >= 0 ? g_mmq_id : env) && ids->ne[1] >= mmq_id_mxfp4_min_tokens() && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS && as->ne[2] <= MMQ_ID_MAX_EXPERTS &&
             mmq_id_mxfp4_lds_bytes(K) <= MMQ_ID_LDS_MAX)
+            r.path = MM_ID_MMQ;
+        return r;
+    }
+    if (blocks) {
+        const act_kind act = mmv_row_for(t)->act;                                                                         // Q8_0 / Q8_1 / Q8_K: the dense mat-vec's image
+        const int64_t wpb = act == ACT_Q8K ? 256 : 32;                                                                    // weights per block
+        if (K < wpb || K % wpb != 0 || K > INT32_MAX || act_image_bytes(act, K) > (size_t) 152 * 1024) return r;           // one column's image in LDS
+        if (as->nb[1] < row_size(t, K)) return r;
+        const size_t al = (t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K) ? 4 : 2;                     // the forms' loads, for every expert's rows
+        if (as->nb[1] % al != 0 || as->nb[2] % al != 0 || ((uintptr_t) as->data & (al - 1)) != 0) return r;
+        r.ok = true; r.act = act;
+        static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
+        if ((g_mmq_id >= 0 ? g_mmq_id : env) && mmq_id_blocks_takes(t) && ids->ne[1] >= mmq_id_blocks_min_tokens() && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS &&
+            as->ne[2] <= MMQ_ID_MAX_EXPERTS && mmq_id_blocks_lds_bytes(K) <= MMQ_ID_LDS_MAX)
             r.path = MM_ID_MMQ;
         return r;
     }

@@ -81,12 +81,13 @@ void mmv_kquant_pair_swiglu(int type, const void * Wg, const void * Wu, size_t w
 //     dst[:, i, t] = as[:, :, ids[i, t]] . b[:, i % b_ne1, t]      -- one (slot i, token t) pair per grid (y, z), the mat-vec bodies of mmv_kquant_multi at one column
 // The launch reads the ids from device memory (a captured graph follows new ids at every replay); an id outside [0, n_expert) is clamped into range before it becomes an address.
 struct mmv_id_args {
-    int          type;                         // GGML_TYPE_Q4_K / Q5_K / Q6_K
+    int          type;                         // GGML_TYPE_Q4_K / Q5_K / Q6_K (mmv_id_kquant), MXFP4 (mmv_id_mxfp4), one of the nine block formats of mmvq.hip (mmv_id_blocks)
     const void * as; size_t as_nb1, as_nb2;    // expert matrices: row stride, expert stride (bytes)
     int64_t      n_expert;
     const void * ids; size_t ids_nb0, ids_nb1; // i32 [n_ids, n_tokens], strided (a view of the argsort result)
     int64_t      n_ids, n_tokens;              // <= 65535 each
-    const void * act;                          // Q8_K images of b's columns: image (t * b_ne1 + i % b_ne1) at that many q8k_image_bytes(K)
+    const void * act;                          // images of b's columns in the type's format (Q8_K for the K-quants; Q8_0 / Q8_1 / Q8_K for the others): image
+                                               // (t * b_ne1 + i % b_ne1) at that many image sizes (q8k_ / q80_ / q81_image_bytes(K))
     int64_t      b_ne1;
     float *      dst; size_t dst_nb1, dst_nb2; // f32 [nrows, n_ids, n_tokens]
     int64_t      K, nrows;
@@ -97,6 +98,11 @@ long mmv_id_launches();
 // 17-byte blocks with no row or expert alignment condition.  Counted apart from the K-quant launches (stat "mmv_id_mxfp4_launches").
 void mmv_id_mxfp4(const mmv_id_args & a, hipStream_t st);
 long mmv_id_mxfp4_launches();
+// the same on experts of the nine block formats (mmvq.hip k_mmv_blocks_id: the dense frame at one column, the Forms unchanged -- the integers and the f32 order of
+// mmv_q8_0 .. mmv_q3_K): type = Q8_0 / Q4_0 / Q5_0 / IQ4_NL (Q8_0 images), Q4_1 / Q5_1 (Q8_1 images), IQ4_XS / Q2_K / Q3_K (Q8_K images); K a multiple of 32 / 256;
+// row stride, expert stride and base 4-byte aligned for Q4_1 / Q5_1 / Q2_K, 2-byte for the rest.  Counted apart (stat "mmv_id_blocks_launches").
+void mmv_id_blocks(const mmv_id_args & a, hipStream_t st);
+long mmv_id_blocks_launches();
 
 // ---- batch-1 decode form (mmv1.hip): ONE activation column, Q4_K / Q6_K, K a multiple of 256 up to 16384 (whole steps of 4096 at the Qwen3-8B widths, TAIL instances otherwise).  The launch takes the f32
 // activation row itself -- x, or rms_norm(x) * norm_w (the RMS_NORM + MUL nodes in front of src1) -- and every workgroup builds the Q8_K
@@ -150,6 +156,13 @@ size_t mmq_id_mxfp4_lds_bytes(int64_t K);               // the slice's dst offse
 void mmq_id_mxfp4(const mmq_id_args & a, hipStream_t st);
 long mmq_id_mxfp4_launches();                           // MXFP4 nodes so far (grouping + matrix launch = one; stat "mmq_id_mxfp4_launches")
 int  mmq_id_mxfp4_last_ks();                            // KS of the most recent mmq_id_mxfp4 launch, 0 before the first (stat "mmq_id_mxfp4_ks"): read-only
+// ---- the same on Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts (mmq_id_blocks.hip): a 32-weight block with an f16 scale and no min term against the Q8_0 images, one int8 MFMA
+// per block -- the integers of ggml_vec_dot_q8_0_q8_0 / _q4_0_q8_0 / _q5_0_q8_0 / _iq4_nl_q8_0.  `m` as for mmv_id_blocks: 2-byte aligned rows and experts.
+bool   mmq_id_blocks_takes(int type);                   // one of the four types
+size_t mmq_id_blocks_lds_bytes(int64_t K);              // as mmq_id_mxfp4_lds_bytes
+void mmq_id_blocks(const mmq_id_args & a, hipStream_t st);
+long mmq_id_blocks_launches();                          // nodes so far (grouping + matrix launch = one; stat "mmq_id_blocks_launches")
+int  mmq_id_blocks_last_ks();                           // KS of the most recent mmq_id_blocks launch, 0 before the first (stat "mmq_id_blocks_ks"): read-only
 // ---- Q4_K weights against a prefill ubatch (> 64 columns) on the int8 matrix cores, tiled (mmq_tile.hip): up to 3 matrices sharing the block-major
 // Q8_K image of the activations (quantize_q8k_tile_image); `resid`: dst = W.x + resid (single matrix, un-split); split-K slabs / deferred reductions as gemm_f16_multi
 struct mmqt_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_t M; const float * resid = nullptr; size_t resid_cs = 0; };

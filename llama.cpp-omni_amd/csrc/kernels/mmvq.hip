@@ -16,7 +16,7 @@
 // every wave keeps >= 2*ROWS KiB in flight; 4-way int8 dot products (v_dot4_i32_i8); wave64 butterfly at
 // the end of each row group.  No bounds branches around loads: addresses are clamped and the contribution
 // of out-of-range lanes is zeroed, so the compiler keeps all loads of a step in one clause.
-#include "../kernels.hpp"
+#include "blocks_dev.hpp"
 
 namespace mi {
 
@@ -133,6 +133,99 @@ __global__ void __launch_bounds__(256) k_mmv_blocks(const char * __restrict__ W,
     }
 }
 
+// MUL_MAT_ID (mixture-of-experts) on experts of the block formats: dst[:, i, t] = as[:, :, ids[i, t]] . b[:, i % b_ne1, t], as k_mmv_id (mmvk.hip) for the K-quants.
+// Grid x = row workgroups, y = slot i, z = token t: every workgroup reads its ONE id from device memory (a captured graph follows the ids of each replay), clamps it
+// into [0, n_expert) before it becomes an address, picks the expert's matrix and the pair's image, and runs the frame above at ONE column: the same stages, clamps and
+// masks, the Forms unchanged -- so the same vec_dot integers and the same f32 summation order as a MUL_MAT of that expert's matrix with that column.  (The frame is
+// written out a second time rather than shared as a device function: shared, the dense kernels' code would no longer be the instructions they were measured with.)
+struct mmv_blocks_id_dev {
+    const char * as; size_t as_nb1, as_nb2; int n_expert;
+    const char * ids; size_t ids_nb0, ids_nb1;
+    const char * act; int b_ne1;
+    char * dst; size_t dst_nb1, dst_nb2;
+    int K, nrows;
+};
+template <class Form, int ROWS>
+__global__ void __launch_bounds__(256) k_mmv_blocks_id(const mmv_blocks_id_dev a) {
+    constexpr int U = Form::U(1), BPS = 64 / Form::LANES;
+    const int i = blockIdx.y, t = blockIdx.z;
+    int id = *(const int *) (a.ids + (size_t) i * a.ids_nb0 + (size_t) t * a.ids_nb1);
+    id = id < 0 ? 0 : (id >= a.n_expert ? a.n_expert - 1 : id);
+    id = __builtin_amdgcn_readfirstlane(id);
+    const int K = a.K, nrows = a.nrows;
+    const size_t w_rs = a.as_nb1;
+    const char * __restrict__ W   = a.as + (size_t) id * a.as_nb2;
+    const char * __restrict__ act = a.act + (size_t) (t * a.b_ne1 + i % a.b_ne1) * Form::image_bytes(K);
+    char * __restrict__ dst       = a.dst + (size_t) i * a.dst_nb1 + (size_t) t * a.dst_nb2;
+
+    const int lane = threadIdx.x & 63;
+    const int g = lane / Form::LANES, part = lane % Form::LANES;
+    const int nb  = K >> Form::LOG2W;
+    const int nit = (nb + BPS * U - 1) / (BPS * U);
+    const int wave   = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nwaves = gridDim.x * 4;
+    const int ngrp   = (nrows + ROWS - 1) / ROWS;
+
+    // no bounds branch around a load: block index and row are clamped, the contribution is zeroed when it is consumed
+    typename Form::regs q[U][ROWS];
+    auto issue = [&](int grp, int it) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            int ib = (it * U + u) * BPS + g; ib = ib < nb ? ib : nb - 1;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                int row = grp * ROWS + r; row = row < nrows ? row : nrows - 1;
+                q[u][r] = Form::load(W + (size_t) row * w_rs + (size_t) ib * Form::BYTES, part);
+            }
+        }
+    };
+    // the first stage is requested before the pair's image is staged; every wave reaches the barrier before any returns
+    int grp = wave, it = 0;
+    if (grp < ngrp) issue(grp, 0);
+    stage_act(act, 0, 1, Form::image_bytes(K));
+    __syncthreads();
+    if (grp >= ngrp) return;
+
+    float acc[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) acc[r] = 0.0f;
+    while (true) {
+        typename Form::regs cq[U][ROWS];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) cq[u][r] = q[u][r];
+        const int cgrp = grp, cit = it;
+        ++it;
+        if (it == nit) { it = 0; grp += nwaves; }
+        const bool more = grp < ngrp;
+        if (more) issue(grp, it);
+
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int  ib    = (cit * U + u) * BPS + g;
+            const bool valid = ib < nb;
+            const typename Form::col y = Form::read(mmv_lds, valid ? ib : nb - 1, part, K, nb);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const bool rv = valid && (cgrp * ROWS + r) < nrows;
+                const float tm = Form::term(Form::decode(cq[u][r], part), y, part);
+                acc[r] += rv ? tm : 0.0f;
+            }
+        }
+        if (cit == nit - 1) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int row = cgrp * ROWS + r;
+                const float s = Form::reduce(acc[r]);
+                if (lane == 0 && row < nrows) *(float *) (dst + (size_t) row * 4) = s;
+                acc[r] = 0.0f;
+            }
+        }
+        if (!more) break;
+    }
+}
+
 // =================================================================================================
 // Q8_0 : 34-B block {f16 d, int8 qs[32]} (ggml-common.h:219-224).  Activation image: qs[K] int8 + per-32 f32 scale.
 //   sumf += sumi * (d_x * d_y)   (ggml-cpu/quants.c:318-327)
@@ -168,8 +261,7 @@ struct q80_form {
 // bytes 8hf .. 8hf+7 = weights 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high); 32 blocks per wave step, U steps per stage.
 template <bool Q5> struct qh_word { uint32_t qh; };            // the fifth bits of a Q5_0 / Q5_1 block: a member of `regs` only where the format has them
 template <> struct qh_word<false> {};
-// fifth bits of 4 consecutive weights (bits b .. b+3 of qh) spread into bit 4 of the four bytes of a word
-static __device__ __forceinline__ uint32_t spread5(uint32_t bits) { return ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) << 4; }
+// (spread5, the fifth bits of 4 consecutive weights into bit 4 of the four bytes of a word: blocks_dev.hpp)
 struct nib_quants { uint32_t lo[2], hi[2]; };                   // the lane's 16 quants, one per byte
 template <bool Q5>
 static __device__ __forceinline__ nib_quants nib_unpack(u32x2 q, uint32_t qh, int hf) {
@@ -242,18 +334,9 @@ struct q40_form {
 //                   sumi = sum_j y.qs[j] * kv[x.qs[j] & 0xF] + y.qs[j + 16] * kv[x.qs[j] >> 4];  sumf += sumi * (d_x * d_y)
 //   IQ4_XS x Q8_K : ggml_vec_dot_iq4_xs_q8_K (x86 :3715; generic :1133-1170) -- the x86 form scales every 32-weight sub-block sum by
 //                   (ls - 32) in integers and converts once per 256-weight super-block: sumi = sum_ib (ls_ib - 32) * sumi_ib;  sumf += sumi * (d_x * d_y)
-// The table lives in four dwords of registers; four indices become four int8 values through two byte permutes (v_perm_b32 over the low
-// and the high 8-byte half of the table) and a per-byte select on the index's bit 3 (v_bfi_b32), then go straight into v_dot4_i32_i8.
+// Four indices become four int8 values through iq4nl_lut4 (blocks_dev.hpp: the table in four dwords of registers, two byte permutes and a per-byte select), then go
+// straight into v_dot4_i32_i8.
 // =================================================================================================
-static __device__ __forceinline__ uint32_t iq4nl_lut4(uint32_t n) {      // n: four indices, one in the low nibble of each byte (upper nibbles zero)
-    const uint32_t T0 = 0xBFAD9881u, T1 = 0xF6EADDCFu, T2 = 0x26190D01u, T3 = 0x71594535u;   // -127 -104 -83 -65 | -49 -35 -22 -10 | 1 13 25 38 | 53 69 89 113
-    const uint32_t i  = n & 0x07070707u;
-    const uint32_t lo = __builtin_amdgcn_perm(T1, T0, i);                 // selector byte k < 4: byte k of T0, 4..7: byte k - 4 of T1
-    const uint32_t hi = __builtin_amdgcn_perm(T3, T2, i);
-    uint32_t m = (n >> 3) & 0x01010101u;
-    m = (m << 8) - m;                                                     // 0xFF in every byte whose index is >= 8 (no borrow crosses a byte)
-    return (hi & m) | (lo & ~m);
-}
 
 // IQ4_NL: 18-B block {f16 d, qs[16]} (2-byte aligned).  Two lanes per block as Q4_0: lane half hf owns qs bytes 8hf .. 8hf+7 = weights
 // 8hf..8hf+7 (low nibbles) and 16+8hf..23+8hf (high); 32 blocks per wave step, U steps per stage.
@@ -763,6 +846,50 @@ void mmv_q4_1(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q41_form
 void mmv_q5_1(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q41_form<true>>(a, st); }
 void mmv_q2_K(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q2k_form>(a, st); }
 void mmv_q3_K(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q3k_form>(a, st); }
+
+// ---- MUL_MAT_ID on experts of the nine block formats (k_mmv_blocks_id): one launch per node, grid sized as mmv_id_kquant (mmvk.hip)
+static long g_mmv_id_blocks_launches = 0;
+long mmv_id_blocks_launches() { return g_mmv_id_blocks_launches; }
+template <class Form>
+static void mmv_id_blocks_launch(const mmv_id_args & a, hipStream_t st) {
+    const size_t lds = Form::image_bytes(a.K);
+    if (a.K < (1 << Form::LOG2W) || a.K % (1 << Form::LOG2W) != 0 || a.K > INT32_MAX || lds > MMV_LDS_MAX || a.n_ids > 65535 || a.n_tokens > 65535 || a.n_expert < 1 || a.b_ne1 < 1 ||
+        a.nrows > INT32_MAX || a.as_nb1 < (size_t) (a.K >> Form::LOG2W) * Form::BYTES) {
+        fprintf(stderr, "[mi355x] mmv_id_blocks: shape out of range (type %d, K=%lld, ids %lld x %lld)\n", a.type, (long long) a.K, (long long) a.n_ids, (long long) a.n_tokens); abort();
+    }
+    // grid.x: every row group of one pair resident at once; with many pairs it shrinks so that the whole launch stays near 4 resident rounds of 1024 workgroups --
+    // each workgroup then grid-strides over the pair's row groups and stages the pair's image once
+    static const int cap = [] { const char * e = getenv("MI355X_MMV_WGS"); const int c = e ? atoi(e) : 1024; return c < 1 ? 1024 : c; }();
+    const int64_t pairs = a.n_ids * a.n_tokens;
+    int64_t gx = ((a.nrows + 1) / 2 + 3) / 4;
+    const int64_t budget = (int64_t) cap * 4 / pairs;
+    if (gx > budget) gx = budget;
+    if (gx < 1) gx = 1;
+    mmv_blocks_id_dev d;
+    d.as = (const char *) a.as; d.as_nb1 = a.as_nb1; d.as_nb2 = a.as_nb2; d.n_expert = (int) a.n_expert;
+    d.ids = (const char *) a.ids; d.ids_nb0 = a.ids_nb0; d.ids_nb1 = a.ids_nb1;
+    d.act = (const char *) a.act; d.b_ne1 = (int) a.b_ne1;
+    d.dst = (char *) a.dst; d.dst_nb1 = a.dst_nb1; d.dst_nb2 = a.dst_nb2;
+    d.K = (int) a.K; d.nrows = (int) a.nrows;
+    if (lds > 64 * 1024) HIP_CHECK(hipFuncSetAttribute((const void *) k_mmv_blocks_id<Form, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    k_mmv_blocks_id<Form, 2><<<dim3((unsigned) gx, (unsigned) a.n_ids, (unsigned) a.n_tokens), dim3(256), lds, st>>>(d);
+    ++g_mmv_id_blocks_launches;
+}
+void mmv_id_blocks(const mmv_id_args & a, hipStream_t st) {
+    if (a.nrows == 0 || a.n_ids == 0 || a.n_tokens == 0) return;
+    switch (a.type) {
+        case GGML_TYPE_Q8_0:   mmv_id_blocks_launch<q80_form>(a, st); break;
+        case GGML_TYPE_Q4_0:   mmv_id_blocks_launch<q40_form<false>>(a, st); break;
+        case GGML_TYPE_Q5_0:   mmv_id_blocks_launch<q40_form<true>>(a, st); break;
+        case GGML_TYPE_IQ4_NL: mmv_id_blocks_launch<iq4nl_form>(a, st); break;
+        case GGML_TYPE_IQ4_XS: mmv_id_blocks_launch<iq4xs_form>(a, st); break;
+        case GGML_TYPE_Q4_1:   mmv_id_blocks_launch<q41_form<false>>(a, st); break;
+        case GGML_TYPE_Q5_1:   mmv_id_blocks_launch<q41_form<true>>(a, st); break;
+        case GGML_TYPE_Q2_K:   mmv_id_blocks_launch<q2k_form>(a, st); break;
+        case GGML_TYPE_Q3_K:   mmv_id_blocks_launch<q3k_form>(a, st); break;
+        default: fprintf(stderr, "[mi355x] mmv_id_blocks: type %d is none of the nine block formats\n", a.type); abort();
+    }
+}
 
 #define MMVF_LAUNCH(NC, ROWS, WF16)                                                                                    \
     do {                                                                                                               \

@@ -13,7 +13,11 @@ rounds show the run-to-run spread.  Per leg and token count:
     TOP/s  = 2 * pairs * M * K int8 operations per node / the grouped path's time.
 MI355X_MMQ_ID_NT4=1 in the environment keeps every tile of the grouped kernel on the four-column-group body (the measurement behind the per-tile branch).
 
-usage: python tools/moe_mmq_bench.py [--reps 3] [--rounds 3] [--tokens 64,128,512,2048]
+--legs blocks: the same for Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts (mmq_id_blocks.hip against mmvq.hip k_mmv_blocks_id), at the Qwen3-30B-A3B gate / up shape and at the
+DeepSeek-V2-Lite down shape (64 experts, 6 used, K 1408, M 2048); --types picks among the four.  MI355X_MMQ_ID_BLOCKS_MIN_TOKENS=65 in the environment puts every token
+count from 65 on the grouped path (the crossover measurement behind MMQ_ID_BLOCKS_MIN_TOKENS, profiles/moe_blocks_crossover.txt).
+
+usage: python tools/moe_mmq_bench.py [--reps 3] [--rounds 3] [--tokens 64,128,512,2048] [--legs kquant|blocks] [--types q8_0,q4_0,q5_0,iq4_nl]
 """
 import argparse
 import os
@@ -25,7 +29,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import load_pkg  # noqa: E402
 
 Q4_K, Q6_K, F32, I32 = 12, 14, 0, 26
-X, XU, E, F = 128, 8, 2048, 768
+BLOCKS = {"q8_0": 8, "q4_0": 2, "q5_0": 6, "iq4_nl": 20}
+E, F = 2048, 768
+KQ_STATS, BL_STATS = ("mmq_id_launches", "mmv_id_launches"), ("mmq_id_blocks_launches", "mmv_id_blocks_launches")      # (grouped, per-pair) launch counters
 HBM = 8.0e12
 
 
@@ -49,6 +55,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--tokens", default="64,128,512,2048")
     ap.add_argument("--min-mib", type=int, default=768)
+    ap.add_argument("--legs", default="kquant", choices=["kquant", "blocks"])
+    ap.add_argument("--types", default="q8_0,q4_0,q5_0,iq4_nl")
     args = ap.parse_args()
     pkg = load_pkg()
     from llama_cpp_omni_amd import qwen3
@@ -56,9 +64,13 @@ def main():
     be = pkg.backend(0)
     rng = np.random.default_rng(0)
     print(f"MI355X_MMQ_ID_NT4={os.environ.get('MI355X_MMQ_ID_NT4', '0')}  reps {args.reps}  rounds {args.rounds}", flush=True)
-    # name, type, K, M (rows per expert), b broadcast over the slots
-    legs = [("gate/up Q4_K", Q4_K, E, F, True), ("down    Q6_K", Q6_K, F, E, False)]
-    for name, ty, K, M, bcast in legs:
+    # name, type, K, M (rows per expert), b broadcast over the slots, experts, experts used, (grouped, per-pair) counters
+    legs = [("gate/up Q4_K", Q4_K, E, F, True, 128, 8, KQ_STATS), ("down    Q6_K", Q6_K, F, E, False, 128, 8, KQ_STATS)]
+    if args.legs == "blocks":
+        legs = []
+        for t in args.types.split(","):
+            legs += [(f"qwen3-30b-a3b gate/up {t}", BLOCKS[t], E, F, True, 128, 8, BL_STATS), (f"deepseek-v2-lite down {t}", BLOCKS[t], 1408, 2048, False, 64, 6, BL_STATS)]
+    for name, ty, K, M, bcast, X, XU, stats in legs:
         tensor_bytes = X * M * row_size(ty, K)
         n_tensors = ((args.min_mib << 20) + tensor_bytes - 1) // tensor_bytes
         n_nodes = max(8, n_tensors)
@@ -85,10 +97,10 @@ def main():
                 for rnd in range(args.rounds):
                     for mode in (1, 0):
                         be.set_option("mmq_id", mode)
-                        key = "mmq_id_launches" if mode else "mmv_id_launches"
+                        key = stats[0] if mode else stats[1]
                         n0, r0 = be.get_stat(key), be.get_stat("graph_replays")
                         t = timed(be, c.graph(), args.reps) / n_nodes
-                        assert be.get_stat(key) - n0 == 2 * n_nodes and be.get_stat("graph_replays") - r0 == 1 + args.reps      # eager + capture ran the launchers, the rest replayed
+                        assert be.get_stat(key) - n0 == 2 * n_nodes and be.get_stat("graph_replays") - r0 == 1 + args.reps, key      # eager + capture ran the launchers (a token count under the path's threshold trips this), the rest replayed
                         us[mode].append(t)
             finally:
                 be.set_option("mmq_id", 1)
