@@ -418,6 +418,8 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmq_id_mxfp4_launches")) return (double) mi::mmq_id_mxfp4_launches();
     if (!strcmp(key, "mmq_id_mxfp4_ks"))    return (double) mi::mmq_id_mxfp4_last_ks();
     if (!strcmp(key, "argsort_launches"))   return (double) mi::argsort_launches();
+    if (!strcmp(key, "ssm_conv_launches"))  return (double) mi::ssm_conv_launches();
+    if (!strcmp(key, "ssm_scan_launches"))  return (double) mi::ssm_scan_launches();
     if (!strcmp(key, "mmv_id_mxfp4_launches")) return (double) mi::mmv_id_mxfp4_launches();
     if (!strcmp(key, "add_id_launches"))    return (double) mi::add_id_launches();
     if (!strcmp(key, "mmv_id_blocks_launches")) return (double) mi::mmv_id_blocks_launches();

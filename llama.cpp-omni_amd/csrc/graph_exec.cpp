@@ -539,6 +539,22 @@ void compute_node(exec_state & s, int i) {
             argsort_f32(td(n->src[0]), (int *) n->data, op_param_i32(n, 0) == 1, s.st); ++s.n_kernels;
             break;
         }
+        case GGML_OP_SSM_CONV: case GGML_OP_SSM_SCAN: {                   // the recurrent layers of Mamba / Mamba-2 (ssm.hip); no fusion: the nodes run one by one
+            // no operand, nor anything up its view chain, may still be a deferred norm's result (Falcon-Mamba / Jamba: RMS_NORM -> MUL in front of dt, B and C), a copy
+            // nobody made (the CONT in front of dt) or a job in the copy queue (the CONCAT in front of the conv)
+            for (int k = 0; k < GGML_MAX_SRC; ++k) for (const ggml_tensor * t = n->src[k]; t; t = view_parent(t)) settle(s, { t });
+            if (!s.lazy.empty()) lazy_net(s, i);
+            copy_flush(s);
+            if (n->op == GGML_OP_SSM_CONV) {
+                prof_scope ps(s, "ssm_conv", (double) nbytes(n->src[0]) + (double) nbytes(n));
+                ssm_conv_f32(td(n->src[0]), td(n->src[1]), td(n), s.st); ++s.n_kernels;
+            } else {
+                const ggml_tensor * st0 = n->src[0], * x = n->src[1];
+                prof_scope ps(s, "ssm_scan", 2.0 * (double) (st0->ne[0] * st0->ne[1] * st0->ne[2] * x->ne[3]) * 4.0);      // the states, read once and written once
+                ssm_scan_f32(td(st0), td(x), td(n->src[2]), td(n->src[3]), td(n->src[4]), td(n->src[5]), (const int *) n->src[6]->data, (float *) n->data, s.st); ++s.n_kernels;
+            }
+            break;
+        }
         case GGML_OP_IM2COL: {
             prof_scope ps(s, "im2col", 0);
             im2col_f32(td(n->src[0]), td(n->src[1]), td(n), n->type, n->op_params, s.st); ++s.n_kernels;

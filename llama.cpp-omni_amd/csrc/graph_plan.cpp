@@ -51,6 +51,31 @@ bool supports_op(const ggml_tensor * op) {
         case GGML_OP_ARGSORT:                                 // one workgroup's LDS holds the padded row (argsort.hip); rows are read through nb1..nb3
             return s0 && s0->type == GGML_TYPE_F32 && op->type == GGML_TYPE_I32 && s0->nb[0] == 4 && is_contiguous(op) && same_shape(s0, op) && argsort_ok(s0->ne[0]) &&
                    (op_param_i32(op, 0) == 0 || op_param_i32(op, 0) == 1);      // enum ggml_sort_order (ggml.h): ASC = 0, DESC = 1
+        case GGML_OP_SSM_CONV: {                              // the asserts of ggml_ssm_conv (ggml.c:5165-5176) and ggml_compute_forward_ssm_conv_f32 (ops.cpp:8520-8523); types, shapes
+                                                              // and strides only -- the loader probes with tensors that have no data (llama-model.cpp:233-256)
+            if (!s0 || !s1 || s0->type != GGML_TYPE_F32 || s1->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32) return false;
+            if (s0->nb[0] != 4 || s0->nb[1] != (size_t) s0->ne[0] * 4 || s1->nb[0] != 4 || op->nb[0] != 4) return false;
+            if (s0->ne[3] != 1 || s1->ne[2] != 1 || s1->ne[3] != 1 || op->ne[3] != 1) return false;
+            if (op->ne[0] != s0->ne[1] || s1->ne[1] != s0->ne[1] || s0->ne[0] != s1->ne[0] - 1 + op->ne[1] || op->ne[2] != s0->ne[2]) return false;
+            return ssm_conv_ok(s1->ne[0], s1->ne[1], op->ne[1], op->ne[2]);          // d_conv 2 .. 8; grid y: tokens (decode) or 64-token tiles, grid z: sequences (<= 65535)
+        }
+        case GGML_OP_SSM_SCAN: {                              // the asserts of ggml_ssm_scan (ggml.c:5198-5235) and ggml_compute_forward_ssm_scan_f32 (ops.cpp:8599-8607); no ->data
+            const ggml_tensor * s = s0, * x = s1, * dt = op->src[2], * A = op->src[3], * B = op->src[4], * Cc = op->src[5], * ids = op->src[6];
+            if (!s || !x || !dt || !A || !B || !Cc || !ids) return false;
+            if (s->type != GGML_TYPE_F32 || x->type != GGML_TYPE_F32 || dt->type != GGML_TYPE_F32 || A->type != GGML_TYPE_F32 || B->type != GGML_TYPE_F32 || Cc->type != GGML_TYPE_F32 ||
+                ids->type != GGML_TYPE_I32 || op->type != GGML_TYPE_F32) return false;
+            if (!is_contiguous(s) || !is_contiguous(dt) || !is_contiguous(A) || !is_contiguous(op) || ids->nb[0] != 4) return false;
+            if (x->nb[0] != 4 || B->nb[0] != 4 || Cc->nb[0] != 4 || x->nb[1] != (size_t) x->ne[0] * 4 || B->nb[1] != (size_t) B->ne[0] * 4 || Cc->nb[1] != (size_t) Cc->ne[0] * 4) return false;
+            if (x->nb[2] % 4 != 0 || x->nb[3] % 4 != 0 || B->nb[2] % 4 != 0 || B->nb[3] % 4 != 0 || Cc->nb[2] % 4 != 0 || Cc->nb[3] % 4 != 0) return false;
+            if (!same_shape(B, Cc)) return false;
+            const int64_t d_state = s->ne[0], head_dim = x->ne[0], n_head = x->ne[1], n_t = x->ne[2], n_s = x->ne[3], n_group = B->ne[1];
+            if (dt->ne[0] != n_head || dt->ne[1] != n_t || dt->ne[2] != n_s || dt->ne[3] != 1 || s->ne[1] != head_dim || s->ne[2] != n_head || s->ne[3] < 1) return false;
+            if (B->ne[0] != d_state || B->ne[2] != n_t || B->ne[3] != n_s || ids->ne[0] != n_s || ids->ne[1] != 1 || ids->ne[2] != 1 || ids->ne[3] != 1) return false;
+            if (A->ne[1] != n_head || A->ne[2] != 1 || A->ne[3] != 1 || (A->ne[0] != 1 && A->ne[0] != d_state)) return false;      // one decay per head (Mamba-2) or per state element (Mamba-1)
+            if (nelements(op) != nelements(x) + d_state * head_dim * n_head * n_s) return false;
+            // d_state 16 / 32 / 64 / 128 / 256 (a row lies on d_state / 4 lanes of one wave), n_head % n_group == 0; grid x: the row groups of a sequence, grid y: sequences (<= 65535)
+            return ssm_scan_ok(d_state, head_dim, n_head, n_group, n_t, n_s);
+        }
         case GGML_OP_ADD: case GGML_OP_SUB: case GGML_OP_MUL: case GGML_OP_DIV:
             return s0 && s1 && s0->type == GGML_TYPE_F32 && s1->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 &&
                    same_shape(s0, op) && can_repeat(s1, s0);

@@ -254,6 +254,15 @@ void sum_rows_f32(const tdesc & x, const tdesc & y, hipStream_t st);            
 bool argsort_ok(int64_t ne0);                  // the padded row fits one workgroup's LDS (ne0 <= 16384)
 void argsort_f32(const tdesc & x, int * dst, bool desc, hipStream_t st);
 long argsort_launches();
+// SSM_CONV / SSM_SCAN (ssm.hip; ops.cpp:8505-8786), f32.  conv: x {d_conv - 1 + n_t, d_inner, n_s} with dense rows, w {d_conv, d_inner} with nb[0] == 4 ->
+// y {d_inner, n_t, n_s}.  scan: s contiguous states, x / B / C with dense rows (strided above), dt and A contiguous, ids i32 read on the device -> dst: y
+// {head_dim, n_head, n_t, n_s} dense, the final states behind it (sequence i3 at i3 * s.nb[3]).  The *_ok forms: the kernels' template range and launch grid.
+bool ssm_conv_ok(int64_t d_conv, int64_t d_inner, int64_t n_t, int64_t n_s);
+void ssm_conv_f32(const tdesc & x, const tdesc & w, const tdesc & y, hipStream_t st);
+bool ssm_scan_ok(int64_t d_state, int64_t head_dim, int64_t n_head, int64_t n_group, int64_t n_t, int64_t n_s);
+void ssm_scan_f32(const tdesc & s, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const int * ids, float * dst, hipStream_t st);
+long ssm_conv_launches();
+long ssm_scan_launches();
 void conv_transpose_1d_f32(const tdesc & w, int w_type, const tdesc & x, const tdesc & y, int s0, hipStream_t st); // ops.cpp:5952-6122
 void cast_f32_i32(const tdesc & src, bool src_is_f32, const tdesc & dst, hipStream_t st);                          // ops.cpp:555, 558-561
 // CPY / CONT / DUP between f32 / f16 with arbitrary strides (same element count)

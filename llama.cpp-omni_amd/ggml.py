@@ -37,6 +37,7 @@ class OP:
     GET_ROWS, SET_ROWS, SOFT_MAX, ROPE, FLASH_ATTN_EXT, UNARY, GLU = 39, 41, 45, 47, 69, 80, 89
     MUL_MAT_ID, ARGSORT = 29, 67
     ADD_ID = 3
+    SSM_CONV, SSM_SCAN = 71, 72
 
 
 class SORT_ORDER:                      # enum ggml_sort_order (ggml.h)
@@ -455,6 +456,10 @@ class Context:
         return T
 
     # ---- views (no data movement)
+    def view_1d(self, a, ne0, offset):
+        T = self._new(a.type, (ne0,), view_src=a, view_offs=offset)
+        return self._op(T, OP.VIEW, [a])
+
     def view_2d(self, a, ne0, ne1, nb1, offset):
         T = self._new(a.type, (ne0, ne1), view_src=a, view_offs=offset)
         T.t.nb[1] = nb1
@@ -539,6 +544,13 @@ class Context:
 
     def scale(self, a, s, b=0.0):
         T = self._new(a.type, a.ne)
+        return self._op(T, OP.SCALE, [a], (_f32_bits(s), _f32_bits(b)))
+
+    def scale_inplace(self, a, s, b=0.0):
+        """ggml_scale_inplace: the result is a view of a (ggml_view_tensor), written where a lies"""
+        T = self._new(a.type, a.ne, view_src=a)
+        for i in range(4):
+            T.t.nb[i] = a.t.nb[i]
         return self._op(T, OP.SCALE, [a], (_f32_bits(s), _f32_bits(b)))
 
     # ---- ops of the Token2Wav graphs (constructors as in ggml.c: result shapes and op_params)
@@ -684,6 +696,48 @@ class Context:
         assert a.ne[0] >= k
         r = self.argsort(a, SORT_ORDER.DESC)
         return self.view_4d(r, k, r.ne[1], r.ne[2], r.ne[3], r.nb[1], r.nb[2], r.nb[3], 0)
+
+    def ssm_conv(self, sx, c):
+        """ggml_ssm_conv (ggml.c:5161-5185): sx [d_conv - 1 + n_t, d_inner, n_s], c [d_conv, d_inner] -> [d_inner, n_t, n_s] f32;
+        dst[r, t, s] = sum_i sx[t + i, r, s] * c[i, r].  The asserts are the reference's (:5165-5176)."""
+        assert sx.ne[3] == 1, "sx is 3-D"
+        assert c.ne[2] == 1 and c.ne[3] == 1, "c is a matrix"
+        d_conv, d_inner = c.ne[0], c.ne[1]
+        n_t, n_s = sx.ne[0] - d_conv + 1, sx.ne[2]
+        assert sx.ne[1] == d_inner
+        assert n_t >= 0
+        T = self._new(GGML_TYPE_F32, (d_inner, n_t, n_s))
+        return self._op(T, OP.SSM_CONV, [sx, c])
+
+    def ssm_scan(self, s, x, dt, A, B, C_, ids):
+        """ggml_ssm_scan (ggml.c:5189-5250): s [d_state, head_dim, n_head, n_rows] states, x [head_dim, n_head, n_t, n_s], dt [n_head, n_t, n_s],
+        A [1 | d_state, n_head], B / C [d_state, n_group, n_t, n_s], ids [n_s] i32 (the state row each sequence starts from) -> 1-D f32: y
+        [head_dim, n_head, n_t, n_s] followed by the final states [d_state, head_dim, n_head, n_s].  The asserts are the reference's (:5198-5235)."""
+        def contiguous(t):
+            blck, size, _ = _TRAITS[t.type]
+            if t.nb[0] != size:
+                return False
+            nb = size * (t.ne[0] // blck)
+            for i in (1, 2, 3):
+                if t.ne[i] != 1 and t.nb[i] != nb:
+                    return False
+                nb *= t.ne[i]
+            return True
+        assert contiguous(s) and contiguous(dt) and contiguous(A)
+        for t in (x, B, C_):
+            size = _TRAITS[t.type][1]
+            assert t.nb[0] == size and t.nb[1] == t.ne[0] * size
+        assert tuple(B.ne) == tuple(C_.ne), "B and C have the same shape"
+        assert ids.type == GGML_TYPE_I32
+        d_state, head_dim, n_head, n_t, n_s = s.ne[0], x.ne[0], x.ne[1], x.ne[2], x.ne[3]
+        assert dt.ne[0] == n_head and dt.ne[1] == n_t and dt.ne[2] == n_s and dt.ne[3] == 1
+        assert s.ne[1] == head_dim and s.ne[2] == n_head
+        assert B.ne[0] == d_state and B.ne[2] == n_t and B.ne[3] == n_s
+        assert ids.ne[0] == n_s and ids.ne[1] == 1 and ids.ne[2] == 1 and ids.ne[3] == 1, "ids is a vector"
+        assert A.ne[1] == n_head and A.ne[2] == 1 and A.ne[3] == 1, "A is a matrix"
+        assert A.ne[0] == 1 or A.ne[0] == d_state, "one decay per head or per state element"
+        T = self._new(GGML_TYPE_F32, (x.nelements() + s.ne[0] * s.ne[1] * s.ne[2] * ids.ne[0],))
+        return self._op(T, OP.SSM_SCAN, [s, x, dt, A, B, C_, ids])
 
     def glu_split(self, a, b, glu_op):
         T = self._new(a.type, a.ne)
