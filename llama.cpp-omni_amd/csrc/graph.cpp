@@ -47,19 +47,7 @@ static uint64_t fingerprint(const ggml_cgraph * g) {
 }
 
 // ------------------------------------------------------------------------------------------------ capture records
-// whole-graph use count of t (ggml_hash_find, ggml-impl.h:257-270: pointer >> 4, linear probing), -1 when the graph carries none
-static inline int whole_use_count(const ggml_cgraph * g, const ggml_tensor * t) {
-    const ggml_hash_set & hs = g->visited_hash_set;
-    const size_t h = ((size_t) (uintptr_t) t >> 4) % hs.size;
-    size_t i = h;
-    while ((hs.used[i >> 5] >> (i & 31)) & 1u) {
-        if (hs.keys[i] == t) return g->use_counts[i];
-        i = (i + 1) % hs.size;
-        if (i == h) break;
-    }
-    return -1;
-}
-static inline bool graph_has_use_counts(const ggml_cgraph * g) { return g->use_counts && g->visited_hash_set.size > 0 && g->visited_hash_set.keys && g->visited_hash_set.used; }
+// (whole_use_count / graph_has_use_counts: graph_internal.hpp, shared with run_nodes)
 static void make_recs(backend_ctx * c, const ggml_cgraph * g, graph_exec & e) {
     e.recs.assign((size_t) g->n_nodes, node_rec());
     std::unordered_map<const ggml_tensor *, int> direct;

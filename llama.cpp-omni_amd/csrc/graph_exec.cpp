@@ -984,26 +984,15 @@ void run_nodes(exec_state & s, ggml_cgraph * g) {
         }
     }
     s.external.clear();
-    if (s.c->opt_fusion && g->use_counts && g->visited_hash_set.size > 0 && g->visited_hash_set.keys && g->visited_hash_set.used) {
+    if (s.c->opt_fusion && graph_has_use_counts(g)) {
         // direct uses inside this cgraph, counted like ggml_build_forward counts them (every src of every node, view nodes included)
         std::unordered_map<const ggml_tensor *, int> direct;
         direct.reserve(g->n_nodes * 2);
         for (int i = 0; i < g->n_nodes; ++i)
             for (int k = 0; k < GGML_MAX_SRC; ++k) if (g->nodes[i]->src[k]) ++direct[g->nodes[i]->src[k]];
-        const ggml_hash_set & hs = g->visited_hash_set;
-        auto whole = [&](const ggml_tensor * t) -> int {                 // ggml_hash_find (ggml-impl.h:257-270): pointer >> 4, linear probing
-            const size_t h = ((size_t) (uintptr_t) t >> 4) % hs.size;
-            size_t i = h;
-            while ((hs.used[i >> 5] >> (i & 31)) & 1u) {
-                if (hs.keys[i] == t) return g->use_counts[i];
-                i = (i + 1) % hs.size;
-                if (i == h) break;
-            }
-            return -1;
-        };
         for (int i = 0; i < g->n_nodes; ++i) {
             const ggml_tensor * t = g->nodes[i];
-            const int w = whole(t);
+            const int w = whole_use_count(g, t);
             auto it = direct.find(t);
             if (w > (it == direct.end() ? 0 : it->second))
                 for (const ggml_tensor * r = t; r; r = r->view_src) s.external.insert(r);     // a view read elsewhere keeps its base's bytes alive too

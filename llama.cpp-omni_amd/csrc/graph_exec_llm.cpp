@@ -974,6 +974,7 @@ bool exec_rope_chain(exec_state & s, int i) {
         if (!(V && idx && V->type == GGML_TYPE_F32 && S->type == GGML_TYPE_F16 && S->nb[0] == 2 && V->nb[0] == 4 && V->ne[0] % A.D == 0 &&
               V->ne[1] == A.T && V->ne[2] == 1 && V->ne[3] == 1 && (idx->type == GGML_TYPE_I64 || idx->type == GGML_TYPE_I32) &&
               idx->ne[0] == A.T && idx->ne[1] == 1 && idx->ne[2] == 1)) continue;
+        if (!ready_before(s, V, i, nullptr, 0)) continue;              // (its rows are READ from memory: not those a chain of this very launch writes -- a k store whose rope has another reader)
         item[ni++] = j;
         if (can_hoist(s, i, j, item, ni)) {
             vj = j;
@@ -1064,6 +1065,9 @@ bool exec_rms_norm(exec_state & s, int i) {
                     if (!(V && idx && V->type == GGML_TYPE_F32 && S->type == GGML_TYPE_F16 && S->nb[0] == 2 && V->nb[0] == 4 && V->ne[0] % A.D == 0 &&
                           V->ne[1] == A.T && V->ne[2] == 1 && V->ne[3] == 1 && (idx->type == GGML_TYPE_I64 || idx->type == GGML_TYPE_I32) &&
                           idx->ne[0] == A.T && idx->ne[1] == 1 && idx->ne[2] == 1)) continue;
+                    // its rows are READ from memory, so they must not be rows a chain of this very launch writes: a k chain whose ROPE result has another reader (an output, a
+                    // later split) is no `store` of that chain, and its SET_ROWS looks like a v store from here
+                    if (!ready_before(s, V, i, nullptr, 0)) continue;
                     item[ni++] = j;
                     if (can_hoist(s, i, j, item, ni)) {
                         vj = j;

@@ -86,6 +86,22 @@ struct mask_map_cache {
     void drop() { mask = nullptr; }      void invalidate(byte_range w) { if (mask && overlap(w, from)) drop(); }
 };
 
+// The scheduler's use counts (ggml_graph_view hands every split the parent's use_counts and visited_hash_set): does the cgraph carry them, and the whole-graph
+// use count of t -- ggml_hash_find (ggml-impl.h:257-270): pointer >> 4, linear probing over the `used` bitset -- or -1 for a tensor the table does not hold.
+// The one probe: run_nodes derives exec_state::external from it, make_recs / recs_match the capture records' `ext`.
+static inline bool graph_has_use_counts(const ggml_cgraph * g) { return g->use_counts && g->visited_hash_set.size > 0 && g->visited_hash_set.keys && g->visited_hash_set.used; }
+static inline int whole_use_count(const ggml_cgraph * g, const ggml_tensor * t) {
+    const ggml_hash_set & hs = g->visited_hash_set;
+    const size_t h = ((size_t) (uintptr_t) t >> 4) % hs.size;
+    size_t i = h;
+    while ((hs.used[i >> 5] >> (i & 31)) & 1u) {
+        if (hs.keys[i] == t) return g->use_counts[i];
+        i = (i + 1) % hs.size;
+        if (i == h) break;
+    }
+    return -1;
+}
+
 struct exec_state {
     backend_ctx * c;
     hipStream_t   st;

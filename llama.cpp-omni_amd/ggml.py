@@ -12,7 +12,7 @@ import numpy as np
 __all__ = [
     "lib_path", "load_library", "Backend", "backend", "Context", "Tensor",
     "GGML_TYPE_F32", "GGML_TYPE_F16", "GGML_TYPE_Q8_0", "GGML_TYPE_Q4_K", "GGML_TYPE_Q6_K", "GGML_TYPE_I32", "GGML_TYPE_I64",
-    "GGML_BACKEND_BUFFER_USAGE_ANY", "GGML_BACKEND_BUFFER_USAGE_WEIGHTS", "GGML_BACKEND_BUFFER_USAGE_COMPUTE", "GGML_ROPE_TYPE_NORMAL", "GGML_ROPE_TYPE_NEOX", "type_traits", "row_size", "OP", "GLU", "UNARY", "SORT_ORDER", "ggml_tensor", "ggml_cgraph",
+    "GGML_BACKEND_BUFFER_USAGE_ANY", "GGML_BACKEND_BUFFER_USAGE_WEIGHTS", "GGML_BACKEND_BUFFER_USAGE_COMPUTE", "GGML_ROPE_TYPE_NORMAL", "GGML_ROPE_TYPE_NEOX", "type_traits", "row_size", "OP", "GLU", "UNARY", "SORT_ORDER", "ggml_tensor", "ggml_cgraph", "ggml_hash_size", "Graph",
 ]
 
 # ------------------------------------------------------------------------------------------------ constants
@@ -389,6 +389,18 @@ def backend(device_index=0):
     return _BACKENDS[device_index]
 
 
+_HASH_PRIMES = (2, 3, 5, 11, 17, 37, 67, 131, 257, 521, 1031, 2053, 4099, 8209, 16411, 32771, 65537, 131101, 262147, 524309, 1048583, 2097169, 4194319,
+                8388617, 16777259, 33554467, 67108879, 134217757, 268435459, 536870923, 1073741827, 2147483659)
+
+
+def ggml_hash_size(min_sz):
+    """ggml_hash_size (reference ggml.c:5845-5869): the smallest of the primes behind the powers of two that is >= min_sz"""
+    for p in _HASH_PRIMES:
+        if p >= min_sz:
+            return p
+    return min_sz | 1
+
+
 class Graph:
     def __init__(self, nodes):
         self.nodes = nodes
@@ -398,6 +410,106 @@ class Graph:
         self.g.n_nodes = len(nodes)
         self.g.n_leafs = 0
         self.g.nodes = C.cast(self.arr, C.POINTER(C.POINTER(ggml_tensor)))
+        self.parent = None
+
+    # ---- what ggml_build_forward_expand leaves behind in a cgraph, and the scheduler's split views of it (Context.graph_parent builds these; a plain Graph has none)
+    def _visit_all(self, leafs, hash_size):
+        """The hash set of every node and leaf and the use counts, as ggml_visit_parents (reference ggml.c:6440-6491) fills them: a tensor takes its slot (ggml_hash_find,
+        ggml-impl.h:257-270: address >> 4 modulo the size, linear probing over the `used` bitset) when it is first met, BEFORE its sources are visited; every src[k] of
+        every node -- view nodes included -- adds one to its source's count."""
+        self.hash_size = hash_size
+        self.keys = (C.c_void_p * hash_size)()
+        self.used = (C.c_uint32 * ((hash_size + 31) >> 5))()
+        self.use_counts = (C.c_int32 * hash_size)()
+        self.leafs = []
+
+        def find(addr):
+            h = (addr >> 4) % hash_size
+            i = h
+            while (self.used[i >> 5] >> (i & 31)) & 1 and self.keys[i] != addr:
+                i = (i + 1) % hash_size
+                assert i != h, "the hash set is full"
+            return i
+
+        def visit(addr):
+            # (iterative: one frame per tensor on the depth-first path, as the reference's recursion)
+            pos = find(addr)
+            if (self.used[pos >> 5] >> (pos & 31)) & 1:
+                return pos
+            stack = []
+
+            def enter(a, p):
+                self.keys[p] = a
+                self.used[p >> 5] |= 1 << (p & 31)
+                self.use_counts[p] = 0
+                stack.append([a, p, 0])
+
+            enter(addr, pos)
+            while stack:
+                a, p, k = stack[-1]
+                t = C.cast(a, C.POINTER(ggml_tensor)).contents
+                if k == 10:
+                    stack.pop()
+                    if t.op == OP.NONE and not (t.flags & 4):
+                        self.leafs.append(a)
+                    if stack:
+                        self.use_counts[p] += 1                # (the parent's `use_counts[src_hash_pos]++` behind the visit)
+                    continue
+                stack[-1][2] = k + 1
+                s = t.src[k]
+                if not s:
+                    continue
+                sa = C.addressof(s.contents)
+                sp = find(sa)
+                if (self.used[sp >> 5] >> (sp & 31)) & 1:
+                    self.use_counts[sp] += 1
+                else:
+                    enter(sa, sp)
+            return pos
+
+        for T in leafs:                                           # spare leaves no node reads: in the table, count 0 (ggml_build_forward_expand called on each of them first)
+            visit(C.addressof(T.t))
+        for T in self.nodes:
+            visit(C.addressof(T.t))
+        self.g.use_counts = C.cast(self.use_counts, C.c_void_p)
+        self.g.visited_hash_set.size = hash_size
+        self.g.visited_hash_set.used = C.cast(self.used, C.c_void_p)
+        self.g.visited_hash_set.keys = C.cast(self.keys, C.c_void_p)
+        self.g.n_leafs = len(self.leafs)
+
+    def slot_of(self, T):
+        """(slot, home slot) of tensor T in the visited hash set; slot is None when the table does not hold it"""
+        addr = C.addressof(T.t)
+        h = (addr >> 4) % self.hash_size
+        i = h
+        while (self.used[i >> 5] >> (i & 31)) & 1:
+            if self.keys[i] == addr:
+                return i, h
+            i = (i + 1) % self.hash_size
+            if i == h:
+                break
+        return None, h
+
+    def use_count(self, T):
+        i, _ = self.slot_of(T)
+        return -1 if i is None else self.use_counts[i]
+
+    def view(self, i0, i1):
+        """ggml_graph_view (reference ggml.c:6696-6711): nodes[i0:i1] of this graph with ITS use counts and hash set -- what the scheduler submits per split"""
+        assert getattr(self, "hash_size", 0) > 0, "Graph.view needs a graph made by Context.graph_parent"
+        assert 0 <= i0 <= i1 <= len(self.nodes)
+        v = Graph.__new__(Graph)
+        v.nodes, v.parent, v.arr = self.nodes[i0:i1], self, self.arr
+        v.hash_size, v.keys, v.used, v.use_counts = self.hash_size, self.keys, self.used, self.use_counts
+        v.g = ggml_cgraph()
+        v.g.size, v.g.n_nodes, v.g.n_leafs = 0, i1 - i0, 0
+        v.g.nodes = C.cast(C.byref(self.arr, i0 * C.sizeof(C.c_void_p)), C.POINTER(C.POINTER(ggml_tensor)))
+        v.g.use_counts = self.g.use_counts
+        v.g.visited_hash_set.size = self.g.visited_hash_set.size
+        v.g.visited_hash_set.used = self.g.visited_hash_set.used
+        v.g.visited_hash_set.keys = self.g.visited_hash_set.keys
+        v.g.order = self.g.order
+        return v
 
 
 def _f32_bits(x):
@@ -836,6 +948,26 @@ class Context:
         if nodes is None and getattr(self, "roots", None):
             return self.graph_expand(self.roots)
         return Graph(list(self.nodes if nodes is None else nodes))
+
+    def graph_parent(self, nodes=None, size=None, leafs=()):
+        """A cgraph that carries what ggml_build_forward_expand leaves behind (reference ggml.c:6440-6470, ggml-impl.h:252-270) when it is called on every node in turn:
+        a visited_hash_set of ggml_hash_size(size) slots holding every node and leaf, its `used` bitset, and use_counts[slot] (one per src[k] of every node, view nodes
+        included).  Graph.view(i0, i1) of it is what the scheduler submits per split (ggml_graph_view).  size: default twice the tensors held, as ggml_new_graph_custom
+        doubles it; leafs: spare leaf tensors no node reads, entered in front of the nodes (they only take slots, and push later keys off their home slots)."""
+        g = Graph(list(self.nodes if nodes is None else nodes))
+        held = {C.addressof(T.t) for T in g.nodes}
+        todo = list(g.nodes)
+        while todo:                                                   # every tensor the table will hold: nodes, and whatever their sources reach
+            t = todo.pop().t
+            for k in range(10):
+                if t.src[k]:
+                    a = C.addressof(t.src[k].contents)
+                    if a not in held:
+                        held.add(a)
+                        todo.append(Tensor(self, t.src[k].contents))
+        held |= {C.addressof(T.t) for T in leafs}
+        g._visit_all(list(leafs), ggml_hash_size(2 * len(held) if size is None else size))
+        return g
 
     def graph_expand(self, roots):
         """Node order of ggml_build_forward_expand() called on `roots` in turn (reference ggml.c ggml_visit_parents: depth-first
