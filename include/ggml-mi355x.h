@@ -73,7 +73,8 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
 /* counters: "graph_replays", "graph_captures", "eager_graphs", "kernels_last_graph", "mmq_tile_launches",
  * "mmv_iq4nl_launches", "mmv_iq4xs_launches", "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches" (launches of the
  * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
- * "argsort_launches", "ssm_conv_launches" / "ssm_scan_launches" (SSM_CONV / SSM_SCAN: one launch per node), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
+ * "argsort_launches", "ssm_conv_launches" / "ssm_scan_launches" (SSM_CONV / SSM_SCAN: one launch per node),
+ * "wkv6_launches" / "gla_launches" / "wkv7_launches" / "l2_norm_launches" (RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM: one launch per node), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
  * "mmq_id_launches" (MUL_MAT_ID nodes of K-quant experts that went through the expert-grouped launchers: the grouping and the matrix launch count as one, and such a
  * node does not touch "mmv_id_launches"), "mmq_id_mxfp4_launches" (the same for MXFP4 experts, counted apart; such a node does not touch "mmv_id_mxfp4_launches"),
  * "mmq_id_mxfp4_ks" (as "mmq_id_ks", for the most recent grouped MXFP4 launch),

@@ -237,6 +237,8 @@ static void be_free(ggml_backend_t b) {
                 mmv_id_launches(), argsort_launches(), mmv_id_mxfp4_launches(), add_id_launches(), mmq_id_launches(), mmq_id_mxfp4_launches(), mmv_id_blocks_launches(), mmq_id_blocks_launches());
     if (getenv("MI355X_LOG_STATS") && (ssm_conv_launches() || ssm_scan_launches()))
         log_msg(GGML_LOG_LEVEL_INFO, "[mi355x] state-space launches (process-wide): ssm_conv=%ld ssm_scan=%ld\n", ssm_conv_launches(), ssm_scan_launches());
+    if (getenv("MI355X_LOG_STATS") && (wkv6_launches() || gla_launches() || wkv7_launches() || l2_norm_launches()))
+        log_msg(GGML_LOG_LEVEL_INFO, "[mi355x] linear-attention launches (process-wide): wkv6=%ld gla=%ld wkv7=%ld l2_norm=%ld\n", wkv6_launches(), gla_launches(), wkv7_launches(), l2_norm_launches());
     if (getenv("MI355X_LOG_STATS"))
         log_msg(GGML_LOG_LEVEL_INFO, "[mi355x] %s: host time inside the backend: graph_compute %ld calls %.1f us avg, set_tensor_async %ld calls %.2f us avg, get_tensor_async %ld calls %.2f us avg, synchronize %ld calls %.1f us avg (includes waiting for the device)\n",
                 c->name.c_str(), c->n_graph, c->n_graph ? c->host_ns_graph * 1e-3 / c->n_graph : 0.0, c->n_set, c->n_set ? c->host_ns_set * 1e-3 / c->n_set : 0.0, c->n_get, c->n_get ? c->host_ns_get * 1e-3 / c->n_get : 0.0,

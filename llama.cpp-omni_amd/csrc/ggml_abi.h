@@ -62,6 +62,7 @@ enum ggml_op {                          // ggml.h:459-566
     GGML_OP_POOL_2D_BACK = 60, GGML_OP_UPSCALE = 61, GGML_OP_PAD = 62, GGML_OP_PAD_REFLECT_1D = 63,
     GGML_OP_ROLL = 64, GGML_OP_ARANGE = 65, GGML_OP_TIMESTEP_EMBEDDING = 66, GGML_OP_ARGSORT = 67,
     GGML_OP_LEAKY_RELU = 68, GGML_OP_FLASH_ATTN_EXT = 69, GGML_OP_SSM_CONV = 71, GGML_OP_SSM_SCAN = 72,
+    GGML_OP_RWKV_WKV6 = 77, GGML_OP_GATED_LINEAR_ATTN = 78, GGML_OP_RWKV_WKV7 = 79,          // ggml.h:541-543
     GGML_OP_UNARY = 80,
     GGML_OP_GLU = 89,
     GGML_OP_COUNT = 90,

@@ -408,6 +408,10 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "argsort_launches"))   return (double) mi::argsort_launches();
     if (!strcmp(key, "ssm_conv_launches"))  return (double) mi::ssm_conv_launches();
     if (!strcmp(key, "ssm_scan_launches"))  return (double) mi::ssm_scan_launches();
+    if (!strcmp(key, "wkv6_launches"))      return (double) mi::wkv6_launches();
+    if (!strcmp(key, "gla_launches"))       return (double) mi::gla_launches();
+    if (!strcmp(key, "wkv7_launches"))      return (double) mi::wkv7_launches();
+    if (!strcmp(key, "l2_norm_launches"))   return (double) mi::l2_norm_launches();
     if (!strcmp(key, "mmv_id_mxfp4_launches")) return (double) mi::mmv_id_mxfp4_launches();
     if (!strcmp(key, "add_id_launches"))    return (double) mi::add_id_launches();
     if (!strcmp(key, "mmv_id_blocks_launches")) return (double) mi::mmv_id_blocks_launches();

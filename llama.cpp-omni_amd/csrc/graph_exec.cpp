@@ -555,6 +555,28 @@ void compute_node(exec_state & s, int i) {
             }
             break;
         }
+        case GGML_OP_RWKV_WKV6: case GGML_OP_GATED_LINEAR_ATTN: case GGML_OP_RWKV_WKV7: case GGML_OP_L2_NORM: {      // the recurrent layers of RWKV6 / RWKV7 (wkv.hip); no fusion
+            // as the SSM cases: the operands are results of NEG, MUL and reshapes of MUL_MAT outputs -- none, nor anything up its view chain, may still be a deferred norm's
+            // result, a copy nobody made or a job in the copy queue
+            for (int k = 0; k < GGML_MAX_SRC; ++k) for (const ggml_tensor * t = n->src[k]; t; t = view_parent(t)) settle(s, { t });
+            if (!s.lazy.empty()) lazy_net(s, i);
+            copy_flush(s);
+            if (n->op == GGML_OP_L2_NORM) {
+                prof_scope ps(s, "l2_norm", (double) nbytes(n->src[0]) + (double) nbytes(n));
+                l2_norm_f32(td(n->src[0]), td(n), op_param_f32(n, 0), s.st); ++s.n_kernels;
+                break;
+            }
+            const ggml_tensor * k = n->src[n->op == GGML_OP_RWKV_WKV7 ? 2 : 0], * state = n->src[n->op == GGML_OP_RWKV_WKV6 ? 5 : n->op == GGML_OP_RWKV_WKV7 ? 6 : 4];
+            const int64_t S = k->ne[0], H = k->ne[1], T = k->ne[2], n_seqs = state->ne[1];
+            auto f = [&](int q) { return (const float *) n->src[q]->data; };
+            prof_scope ps(s, n->op == GGML_OP_RWKV_WKV6 ? "wkv6" : n->op == GGML_OP_RWKV_WKV7 ? "wkv7" : "gla", 2.0 * (double) (S * S * H * n_seqs) * 4.0);      // the states, read once and written once
+            if (n->op == GGML_OP_RWKV_WKV6 && nelements(n->src[3]) != S * H) { log_msg(GGML_LOG_LEVEL_ERROR, "[mi355x] graph_compute: RWKV_WKV6 %s: time_first has %lld elements, not %lld\n", n->name, (long long) nelements(n->src[3]), (long long) (S * H)); abort(); }
+            if (n->op == GGML_OP_RWKV_WKV6)      wkv6_f32(f(0), f(1), f(2), f(3), f(4), f(5), (float *) n->data, S, H, T, n_seqs, s.st);
+            else if (n->op == GGML_OP_RWKV_WKV7) wkv7_f32(f(0), f(1), f(2), f(3), f(4), f(5), f(6), (float *) n->data, S, H, T, n_seqs, s.st);
+            else                                 gla_f32(f(0), f(1), f(2), f(3), f(4), op_param_f32(n, 0), (float *) n->data, S, H, T, n_seqs, s.st);
+            ++s.n_kernels;
+            break;
+        }
         case GGML_OP_IM2COL: {
             prof_scope ps(s, "im2col", 0);
             im2col_f32(td(n->src[0]), td(n->src[1]), td(n), n->type, n->op_params, s.st); ++s.n_kernels;

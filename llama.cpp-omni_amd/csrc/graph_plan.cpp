@@ -76,6 +76,28 @@ bool supports_op(const ggml_tensor * op) {
             // d_state 16 / 32 / 64 / 128 / 256 (a row lies on d_state / 4 lanes of one wave), n_head % n_group == 0; grid x: the row groups of a sequence, grid y: sequences (<= 65535)
             return ssm_scan_ok(d_state, head_dim, n_head, n_group, n_t, n_s);
         }
+        case GGML_OP_RWKV_WKV6: case GGML_OP_GATED_LINEAR_ATTN: case GGML_OP_RWKV_WKV7: {
+            // the asserts of ggml_rwkv_wkv6 / ggml_gated_linear_attn / ggml_rwkv_wkv7 (ggml.c:5369-5499); types, shapes and strides only -- the loader probes WKV6 with S = H =
+            // n_tokens = n_seqs = 123, a 4-D state {S, n_seqs, S, H} and no data (llama-model.cpp:257-271)
+            const int n_src = op->op == GGML_OP_RWKV_WKV6 ? 6 : op->op == GGML_OP_RWKV_WKV7 ? 7 : 5;
+            const ggml_tensor * k = op->src[op->op == GGML_OP_RWKV_WKV7 ? 2 : 0], * state = op->src[n_src - 1];
+            if (!k || !state || op->type != GGML_TYPE_F32 || !is_contiguous(op)) return false;
+            const int64_t S = k->ne[0], H = k->ne[1], T = k->ne[2], n_seqs = state->ne[1];
+            for (int q = 0; q < n_src; ++q) {
+                const ggml_tensor * t = op->src[q];
+                if (!t || t->type != GGML_TYPE_F32 || !is_contiguous(t)) return false;
+                if (t == state) continue;
+                // time_first: the constructor asserts no shape, and the loader's probe passes the file's own {head_size, n_head} weight beside its 123-sized operands --
+                // a refusal there sends the weight to the CPU.  A graph that reaches the executor with anything but S * H elements is an error there.
+                if (op->op == GGML_OP_RWKV_WKV6 && q == 3) { if (nelements(t) < 1) return false; continue; }
+                if (t->ne[0] != S || t->ne[1] != H || t->ne[2] != T || t->ne[3] != 1) return false;
+            }
+            if (!wkv_ok(S, H, T, n_seqs)) return false;               // 1 <= S <= 128, T % n_seqs == 0, grid y: heads, grid z: sequences (<= 65535 each)
+            return nelements(state) == S * S * H * n_seqs && op->ne[0] == S * H && op->ne[1] == T + S * n_seqs && op->ne[2] == 1 && op->ne[3] == 1;
+        }
+        case GGML_OP_L2_NORM:                                 // ggml_compute_forward_l2_norm_f32 (ops.cpp:3858-3899): f32 rows with nb[0] == 4, read through nb1..nb3; eps >= 0
+            return s0 && s0->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && s0->nb[0] == 4 && op->nb[0] == 4 && same_shape(s0, op) && op_param_f32(op, 0) >= 0.0f &&
+                   l2_norm_ok(s0->ne[0], nrows(s0));
         case GGML_OP_ADD: case GGML_OP_SUB: case GGML_OP_MUL: case GGML_OP_DIV:
             return s0 && s1 && s0->type == GGML_TYPE_F32 && s1->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 &&
                    same_shape(s0, op) && can_repeat(s1, s0);

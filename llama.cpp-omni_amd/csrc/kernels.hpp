@@ -263,6 +263,19 @@ bool ssm_scan_ok(int64_t d_state, int64_t head_dim, int64_t n_head, int64_t n_gr
 void ssm_scan_f32(const tdesc & s, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const int * ids, float * dst, hipStream_t st);
 long ssm_conv_launches();
 long ssm_scan_launches();
+// RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM (wkv.hip; ops.cpp:9177, :9393, :9598, :3858), f32.  The WKV operands are contiguous {S, H, T} (tf {S, H}), the state source
+// n_seqs * S * S * H contiguous floats of any shape; dst {S * H, T + S * n_seqs}: the outputs, then the new states.  wkv_ok: the head sizes with a kernel (1 .. 128) and the launch
+// grid (heads and sequences <= 65535 each, T a multiple of n_seqs).  l2_norm: rows through nb1..nb3, nb[0] == 4.
+bool wkv_ok(int64_t S, int64_t H, int64_t T, int64_t n_seqs);
+void wkv6_f32(const float * k, const float * v, const float * r, const float * tf, const float * td, const float * state, float * dst, int64_t S, int64_t H, int64_t T, int64_t n_seqs, hipStream_t st);
+void gla_f32(const float * k, const float * v, const float * q, const float * g, const float * state, float scale, float * dst, int64_t S, int64_t H, int64_t T, int64_t n_seqs, hipStream_t st);
+void wkv7_f32(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b, const float * state, float * dst, int64_t S, int64_t H, int64_t T, int64_t n_seqs, hipStream_t st);
+bool l2_norm_ok(int64_t ne0, int64_t n_rows);
+void l2_norm_f32(const tdesc & x, const tdesc & y, float eps, hipStream_t st);
+long wkv6_launches();
+long gla_launches();
+long wkv7_launches();
+long l2_norm_launches();
 void conv_transpose_1d_f32(const tdesc & w, int w_type, const tdesc & x, const tdesc & y, int s0, hipStream_t st); // ops.cpp:5952-6122
 void cast_f32_i32(const tdesc & src, bool src_is_f32, const tdesc & dst, hipStream_t st);                          // ops.cpp:555, 558-561
 // CPY / CONT / DUP between f32 / f16 with arbitrary strides (same element count)

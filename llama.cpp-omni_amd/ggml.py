@@ -38,6 +38,7 @@ class OP:
     MUL_MAT_ID, ARGSORT = 29, 67
     ADD_ID = 3
     SSM_CONV, SSM_SCAN = 71, 72
+    L2_NORM, RWKV_WKV6, GATED_LINEAR_ATTN, RWKV_WKV7 = 27, 77, 78, 79
 
 
 class SORT_ORDER:                      # enum ggml_sort_order (ggml.h)
@@ -850,6 +851,48 @@ class Context:
         assert A.ne[0] == 1 or A.ne[0] == d_state, "one decay per head or per state element"
         T = self._new(GGML_TYPE_F32, (x.nelements() + s.ne[0] * s.ne[1] * s.ne[2] * ids.ne[0],))
         return self._op(T, OP.SSM_SCAN, [s, x, dt, A, B, C_, ids])
+
+    @staticmethod
+    def _contiguous(t):
+        blck, size, _ = _TRAITS[t.type]
+        if t.nb[0] != size:
+            return False
+        nb = size * (t.ne[0] // blck)
+        for i in (1, 2, 3):
+            if t.ne[i] != 1 and t.nb[i] != nb:
+                return False
+            nb *= t.ne[i]
+        return True
+
+    def l2_norm(self, a, eps):
+        """ggml_l2_norm (ggml.c:3018-3044): y = x / max(sqrt(sum x^2), eps) per row, same shape; op_params[0] = eps"""
+        T = self._new(a.type, a.ne)
+        return self._op(T, OP.L2_NORM, [a], (_f32_bits(eps),))
+
+    def _wkv(self, op, like, srcs, state, params=()):
+        """the common part of ggml_rwkv_wkv6 / ggml_gated_linear_attn / ggml_rwkv_wkv7 (ggml.c:5369-5499): every source contiguous, the operands in `like` shaped
+        {S, H, n_tokens} as k, nelements(state) == S * S * H * n_seqs with n_seqs = state.ne[1] -> f32 {S * H, n_tokens + S * n_seqs}: the outputs, then the new states"""
+        for t in srcs:
+            assert self._contiguous(t)
+        k = like[0]
+        S, H, n_tokens, n_seqs = k.ne[0], k.ne[1], k.ne[2], state.ne[1]
+        for t in like:
+            assert t.ne[0] == S and t.ne[1] == H and t.ne[2] == n_tokens
+        assert state.nelements() == S * S * H * n_seqs
+        T = self._new(GGML_TYPE_F32, (S * H, n_tokens + S * n_seqs, 1, 1))
+        return self._op(T, op, srcs, params)
+
+    def rwkv_wkv6(self, k, v, r, tf, td, state):
+        """ggml_rwkv_wkv6 (ggml.c:5369-5408): k, v, r, td {S, H, n_tokens}, tf {S, H} (no shape assert, as the reference), state"""
+        return self._wkv(OP.RWKV_WKV6, [k, v, r, td], [k, v, r, tf, td, state], state)
+
+    def gated_linear_attn(self, k, v, q, g, state, scale):
+        """ggml_gated_linear_attn (ggml.c:5412-5451): k, v, q, g {S, H, n_tokens}, state; op_params[0] = scale"""
+        return self._wkv(OP.GATED_LINEAR_ATTN, [k, v, q, g], [k, v, q, g, state], state, (_f32_bits(scale),))
+
+    def rwkv_wkv7(self, r, w, k, v, a, b, state):
+        """ggml_rwkv_wkv7 (ggml.c:5455-5499): w, k, v, a, b {S, H, n_tokens} (r: contiguous, no shape assert, as the reference), state"""
+        return self._wkv(OP.RWKV_WKV7, [k, w, v, a, b], [r, w, k, v, a, b, state], state)
 
     def glu_split(self, a, b, glu_op):
         T = self._new(a.type, a.ne)

@@ -7,7 +7,7 @@ export GGML_BACKEND_PATH="$PWD/llama.cpp-omni_amd/lib/libggml-mi355x.so"
 export LD_LIBRARY_PATH="$PWD/oracle/_ref:$LD_LIBRARY_PATH"
 mkdir -p gpurun_out
 OPS="$@"
-[ -z "$OPS" ] && OPS="MUL_MAT ADD SUB MUL DIV RMS_NORM SCALE ROPE SOFT_MAX CPY CONT DUP GET_ROWS SET_ROWS FLASH_ATTN_EXT SWIGLU REGLU GEGLU GEGLU_ERF GEGLU_QUICK ABS SGN NEG STEP TANH ELU RELU SIGMOID GELU GELU_QUICK SILU HARDSWISH HARDSIGMOID EXP GELU_ERF NORM IM2COL POOL_2D SQR SQRT LOG SIN COS CLAMP LEAKY_RELU CONCAT REPEAT PAD PAD_REFLECT_1D ARANGE TIMESTEP_EMBEDDING SUM_ROWS CONV_TRANSPOSE_1D SSM_CONV SSM_SCAN"
+[ -z "$OPS" ] && OPS="MUL_MAT ADD SUB MUL DIV RMS_NORM SCALE ROPE SOFT_MAX CPY CONT DUP GET_ROWS SET_ROWS FLASH_ATTN_EXT SWIGLU REGLU GEGLU GEGLU_ERF GEGLU_QUICK ABS SGN NEG STEP TANH ELU RELU SIGMOID GELU GELU_QUICK SILU HARDSWISH HARDSIGMOID EXP GELU_ERF NORM IM2COL POOL_2D SQR SQRT LOG SIN COS CLAMP LEAKY_RELU CONCAT REPEAT PAD PAD_REFLECT_1D ARANGE TIMESTEP_EMBEDDING SUM_ROWS CONV_TRANSPOSE_1D SSM_CONV SSM_SCAN RWKV_WKV6 GATED_LINEAR_ATTN RWKV_WKV7 L2_NORM"
 rc=0
 for op in $OPS; do
   timeout ${TBO_TIMEOUT:-2400} ./oracle/_ref/test-backend-ops test -b MI355X0 -o $op > gpurun_out/tbo_$op.log 2>&1
