@@ -81,6 +81,8 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
  * "mmv_id_blocks_launches" (MUL_MAT_ID launches on Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL / IQ4_XS / Q2_K / Q3_K experts, counted apart from "mmv_id_launches"),
  * "mmq_id_blocks_launches" (grouped nodes of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts, counted apart; such a node does not touch "mmv_id_blocks_launches"),
  * "mmq_id_blocks_ks" (as "mmq_id_ks", for the most recent of those),
+ * "mv2_launches" (launches of the LDS-DMA decode mat-vec engine, csrc/kernels/mmv2.hip: one per mmv2() call -- a launch of the register family does not count),
+ * "mv2_cus" (not a counter: the CU count the engine partitions its launches with on this backend's device),
  * "mmq_id_ks" (not a counter: the K split -- waves per tile, 1 / 2 / 4 / 8 -- of the most recent expert-grouped launch, 0 before the first; which k_mmq_id instantiation ran)
  * (all of them process-wide; a replayed graph re-runs captured launches without counting them),
  * "shadow_bytes", "shadow_tensors", "prof_mmv_q4k_us", "prof_mmv_q4k_n", "prof_mmv_q4k_bytes", ....

@@ -389,6 +389,8 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "norm_from_split_launches")) return (double) mi::norm_from_split_launches();
     if (!strcmp(key, "norm_rope_split_launches")) return (double) mi::norm_rope_split_launches();
     if (!strcmp(key, "mmq_tile_launches"))  return (double) mi::mmq_tile_launches();
+    if (!strcmp(key, "mv2_launches"))       return (double) mi::mmv2_launches();
+    if (!strcmp(key, "mv2_cus"))            return (double) mi::mv2_cus_of(c->device);
     if (!strcmp(key, "gemm_kq_launches"))   return (double) mi::gemm_variant_launches(3);
     if (!strcmp(key, "fattn_dma_launches")) return (double) mi::fattn_dma_launches();
     if (!strcmp(key, "attn_vrows_launches")) return (double) mi::attn_vrows_launches();

@@ -472,7 +472,14 @@ void exec_mul_mat(exec_state & s, int i) {
         // the engine's residual staging holds -- drop the epilogue fusion rather than the batch-1 kernel
         mv1_args t; t.nmat = nm; t.K = K; t.img = (const void *) 16;
         for (int q = 0; q < nm; ++q) t.m[q] = a.m[q];
-        if (!mmv1_ok(t)) {
+        // (K-quants: the register family takes any residual, so mmv1_ok alone kept the epilogue and lost the engine -- ask the engine itself, with the source the launch
+        //  will get: a pending norm at K = 12288 it refuses either way)
+        bool drop = !mmv1_ok(t);
+        if (!drop && !q80 && mmv2_enabled()) {
+            mv1_args e = t; e.img = nullptr; e.x = (const float *) 16; e.norm_w = s.pn.m && x == s.pn.m ? (const float *) 16 : nullptr;
+            if (!mmv2_ok(e)) { for (int q = 0; q < nm; ++q) e.m[q].resid = nullptr; drop = mmv2_ok(e); }
+        }
+        if (drop) {
             for (int q = 0; q < nm; ++q) if (add_idx[q] >= 0) {
                 ggml_tensor * c = g->nodes[mm_idx[q]];
                 a.m[q].resid = nullptr; a.m[q].resid_cs = 0; a.m[q].dst = (float *) c->data; a.m[q].dst_cs = c->nb[1];

@@ -124,6 +124,8 @@ bool mmv2_ok(const mv1_args & a);
 void mmv2(const mv1_args & a, hipStream_t st);
 void mmv2_enable(bool on);
 bool mmv2_enabled();                                // (mmv1() routes to the engine)
+long mmv2_launches();                               // mmv2() calls so far (stat "mv2_launches"): read-only, what tells the engine from the register family
+int  mv2_cus_of(int device);                        // the CU count the engine plans a launch with on `device` (stat "mv2_cus")
 bool mmv1q_ok(const mv1_args & a);
 void mmv1q(const mv1_args & a, hipStream_t st);
 

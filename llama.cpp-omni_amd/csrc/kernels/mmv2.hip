@@ -170,13 +170,17 @@ namespace mi {
 // per-device state (the omni pinning map puts the LLM on a device other than the first one that launched this kernel): CU count and the
 // dynamic-LDS attribute of each instantiation are tracked per device ordinal
 static int mv2_dev_ordinal() { int dev = 0; HIP_CHECK(hipGetDevice(&dev)); return dev >= 0 && dev < 64 ? dev : 0; }
-int mv2_cus() {
+int mv2_cus_of(int dev) {                              // (stat "mv2_cus": the backend's device, whichever is current)
     static int n[64] = { 0 };
-    const int dev = mv2_dev_ordinal();
+    if (dev < 0 || dev >= 64) dev = 0;
     if (!n[dev]) { hipDeviceProp_t p; HIP_CHECK(hipGetDeviceProperties(&p, dev)); n[dev] = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256; }
     return n[dev];
 }
+int mv2_cus() { return mv2_cus_of(mv2_dev_ordinal()); }
+static long g_mv2_launches = 0;
+long mmv2_launches() { return g_mv2_launches; }
 
+// (tests/test_mv2_partition_gpu.py pins what is accepted here at its edges: the residual staging limit, rows < CUs, every group form)
 bool mmv2_ok(const mv1_args & a) {
     if (a.nmat < 1 || a.nmat > 3 || (a.K != 4096 && a.K != 12288)) return false;
     if (a.K == 12288 && a.norm_w && !a.img) return false;                                    // (the staging area holds the row OR row + norm weights of 4096)
@@ -227,6 +231,7 @@ static void mv2_launch(const mv2_dev & d, int grid, hipStream_t st, const float 
 #ifndef MV2_Q6_SHARE
 #define MV2_Q6_SHARE 1.7                      // tools/mmv3_lab.hip, qkv with a Q6_K v: 1.0 6.46 us, 1.3 5.97, 1.6 5.95, 2.0 5.85, 2.5 6.59
 #endif
+// (tests/test_mv2_partition_gpu.py restates this partition and pins it: ragged q / r, rows < workgroups, a member with more workgroups than rows)
 static int mv2_plan(const mv1_args & a, mv2_dev & d, int & tm) {
     const int cus = mv2_cus();
     double bytes[3], total = 0; int64_t tasks = 0; tm = 0;
@@ -262,6 +267,7 @@ void mmv2(const mv1_args & a, hipStream_t st) {
     if (!mmv2_ok(a)) { fprintf(stderr, "[mi355x] mmv2: unsupported arguments (K=%lld)\n", (long long) a.K); abort(); }
     mv2_dev d; int tm;
     const int grid = mv2_plan(a, d, tm);
+    ++g_mv2_launches;
     const bool pair = a.W_up != nullptr;
     // waves per workgroup (1 loader + the consumers), by launch shape: tools/mmv2_lab.hip sweep (profiles/r06_mv2_waves.txt).  The long pair launch keeps sixteen; the short
     // ones run faster with fewer waves contending for the CU's issue slots through the prologue and the tail: the three-matrix group with twelve (6.4 -> 6.1 us; nine with
