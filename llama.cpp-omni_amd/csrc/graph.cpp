@@ -381,6 +381,7 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "copies_forwarded"))   return (double) c->stat_copies_forwarded;
     if (!strcmp(key, "copies_dropped"))     return (double) c->stat_copies_dropped;
     if (!strcmp(key, "lazy_conts_materialised")) return (double) c->stat_lazy_materialised;
+    if (!strcmp(key, "concat_tails"))       return (double) c->stat_concat_tails;
     if (!strncmp(key, "shadow_", 7))        return mi::shadow_stat(key);
     if (!strcmp(key, "gemm256_launches"))   return (double) mi::gemm_variant_launches(0);
     if (!strcmp(key, "gemm192_launches"))   return (double) mi::gemm_variant_launches(1);

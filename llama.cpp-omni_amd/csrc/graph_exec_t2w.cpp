@@ -713,6 +713,7 @@ bool exec_concat_tail(exec_state & s, int i) {
         else { copy_flush(s); cpy_strided(src, GGML_TYPE_F32, td(n3), GGML_TYPE_F32, s.st); ++s.n_kernels; }      // (x may be the output of a copy still queued)
     }
     note_write(s, n3);
+    ++s.c->stat_concat_tails;
     for (int k : { n0 ? j1 : -1, j2, j3 }) if (k >= 0) { s.done[k] = 1; ++s.n_fused; }
     return true;
 }

@@ -133,7 +133,7 @@ def test_concat_tail_reads_a_queued_copy(pkg, be, ref_be, tail):
         n0 = c.cont(x)
         n1 = c.concat(cache, n0, 1)                                     # [C, P + dt]
         n2 = c.cont(n1)
-        v = c.view_2d(n2, C_, keep, n2.t.nb[1], (P + dt - keep) * n2.t.nb[1])
+        v = c.view_3d(n2, C_, keep, 1, n2.t.nb[1], n2.t.nb[2], (P + dt - keep) * n2.t.nb[1])      # (a 3-D view, as the reference's builder: the matcher compares nb[2], which a 2-D view sets otherwise)
         n3 = c.cont(v)
         return dict(xin=xin, cache=cache), [n3]
 
@@ -143,10 +143,11 @@ def test_concat_tail_reads_a_queued_copy(pkg, be, ref_be, tail):
     if tail == "direct":
         be.set_option("copy_batch", 0)
     try:
-        k_on, k_off, _ = drive(pkg, be, ref_be, build, feeds, 0)
+        k_on, k_off, moved = drive(pkg, be, ref_be, build, feeds, 0, stats=("concat_tails",))
     finally:
         be.set_option("copy_batch", -1)
     assert k_on < k_off, (k_on, k_off)                                  # CONT + CONCAT + CONT + CONT ran as one copy
+    assert moved["concat_tails"] == 1, moved                            # ... by exec_concat_tail (the copy queue alone gives the same count)
 
 
 # ------------------------------------------------------------------------------------------------ rt

@@ -32,7 +32,17 @@ try_alias_vt (:1364-1388).  Two sites write their f32 rows whatever the guard sa
 (:858-870: the image is one more output of the kernel) -- so they have control and output only: a split of them cannot fail, as a build whose `external` stays empty
 confirms (every other split, view, crowded and flip case fails under it).  The same holds for the residual ADD in front of the RMS_NORM that sums its split-K slabs: the
 norm launch writes the ADD's rows itself, so only the mat-mul in front of it is observed there.
-Waiting for a follow-up (graph_exec_t2w.cpp): the f32 attention chain, the modulated norm, the gate norm, lazy copies, the causal convolution, the concat tail, conv1d.
+
+The encoder / Token2Wav side, by the line of its guard -- graph_exec_t2w.cpp: exec_attn_f32 (:107 K.Q, :117 SCALE, :123 SOFT_MAX, :146 the second product, :155 the views in front
+of the CONT), match_norm_modulate for exec_norm_modulate and behind exec_gate_norm (:13 NORM, :24 MUL, :25 the first ADD), exec_gate_norm's gate MUL (:57), exec_causal_conv
+(:557, :606, :619, :620), exec_concat_tail (:676, :681, :689), exec_conv1d_tc (:730, :744, :749, :765, :772, :776, :781), lazy_try_register (:397, :409: cases A / B in front
+of the causal convolution, C / C' in front of the attention chain; an observed copy is never registered, so lazy_net / the matchers' erasing of a record cannot lose it), and
+graph_exec.cpp copy_prune (:867: a forwarded copy nobody reads any more is never launched).  For the lazy sites the observed run must also leave fewer copies un-run than the
+control (lazy_conts) and launch more kernels or count a materialisation.  Every protocol starts with the backend's captures dropped (_fresh): a Run's node records and device
+addresses repeat those of the test before it.  exec_gate_norm writes x = resid + y * gate in every case (it is the norm launch's second output): output only.  exec_concat_tail
+compares nb[2] of the tail VIEW with the copy's, which a 2-D view never meets: its site has a batch dimension, and the concat_tails counter, not the launch count (the copy
+queue's with or without the matcher), proves its control.  Against a build whose `external` stays empty every new split, view, crowded and flip case fails by assertion (the
+interior node keeps its NaNs, or the bytes of the other layout), with nothing that cannot fail but gate_norm / x; every guard named here was found in place on the device.
 """
 import numpy as np
 import pytest
@@ -50,8 +60,10 @@ N_SETS = 3
 class Case:
     """one site's graph on one backend: c (Context), obs {name: (interior Tensor, bar)}, outs [(Tensor, bar)], set(k) writes input set k, order = the nodes to submit"""
 
-    def __init__(self, c, obs, outs, set_, order=None, close=None):
+    def __init__(self, c, obs, outs, set_, order=None, close=None, alloc=None, f64=None):
         self.c, self.obs, self.outs, self.set, self.order, self._close = c, obs, outs, set_, list(c.nodes if order is None else order), close
+        self.alloc = alloc or {}                                        # keyword arguments of Context.alloc (usage=WEIGHTS: the sites that keep a resident kernel image)
+        self.f64 = f64                                                  # f64(k) -> the outputs of input set k restated in float64 (None: not restated), bar F64_BAR
 
     def close(self):
         self.c.free()
@@ -59,15 +71,22 @@ class Case:
             self._close()
 
 
-def _simple(pkg, backend, build, feeds):
+def _simple(pkg, backend, build, feeds, alloc=None, once=(), f64=None):
+    """once: inputs written by the first set() only, from set 0 (a convolution kernel: writing it again drops its resident image, and no image is made inside a capture)"""
     c = pkg.Context(backend)
     ins, obs, outs = build(c)
     sets = [feeds(np.random.default_rng(seed)) for seed in (11, 12, 13)]
+    first = [True]
 
     def set_(k):
         for name, T in ins.items():
-            backend.tensor_set(T, sets[k % N_SETS][name])
-    return Case(c, obs, outs, set_)
+            if name in once:
+                if first[0]:
+                    backend.tensor_set(T, sets[0][name])
+            else:
+                backend.tensor_set(T, sets[k % N_SETS][name])
+        first[0] = False
+    return Case(c, obs, outs, set_, alloc=alloc, f64=(lambda k: f64(dict(sets[k % N_SETS], **{n: sets[0][n] for n in once}))) if f64 else None)
 
 
 def _get(backend, T):
@@ -88,7 +107,12 @@ def _cmp(a, b, bar, what):
     a, b = a.astype(np.float32), b.astype(np.float32)
     assert np.isfinite(a).all(), (what, "not finite", int((~np.isfinite(a)).sum()))
     e = nmse(a, b)
+    _WORST[0] = max(_WORST[0], (e / bar, e, bar))
     assert e < bar, (what, e, bar)
+
+
+_WORST = [(0.0, 0.0, 0.0)]                                              # (the comparison closest to its bar since _three_runs last reset it: printed, never asserted)
+F64_BAR = 1e-10                                                         # a float64 restatement beside the reference backend (test_round5_gpu.py:336)
 
 
 _REF = {}
@@ -101,7 +125,7 @@ def _reference(pkg, ref_be, name):
         c = case.c
         if c.buffer:
             c.free()
-        c.alloc()
+        c.alloc(**case.alloc)
         g = c.graph(case.order)
         runs = []
         for k in range(N_SETS):
@@ -136,7 +160,7 @@ class Run:
         self.nodes = nodes + behind
         if c.buffer:
             c.free()
-        c.alloc()
+        c.alloc(**case.alloc)
         self.graphs = {}
         self.spares = None
         if crowded:
@@ -193,22 +217,39 @@ class Run:
         self.case.close()
 
 
+def _fresh(be):
+    """every capture the backend holds is dropped (set_option does that): a run's first submission is eager, not the capture or the replay of an equal-looking graph of the
+    test before it -- node records and device addresses repeat from one Run to the next, and a capture cannot make a resident kernel image"""
+    be.set_option("fusion", 1)
+
+
 def _three_runs(pkg, be, ref_be, name, key, variant, crowded=False):
     ref = _reference(pkg, ref_be, name)
+    _fresh(be)
     run = Run(pkg, be, name, key, variant, crowded)
     try:
         r0 = be.get_stat("graph_replays")
         k_first = None
+        _WORST[0] = (0.0, 0.0, 0.0)
+        before = {s: be.get_stat(s) for s in LAZY_STATS}
         for k, what in enumerate(("eager run", "captured run", "replayed run")):
             got = run.submit(k)
             if k == 0:
                 k_first = run.kernels
+                run.moved = {s: be.get_stat(s) - before[s] for s in LAZY_STATS}       # (of the eager run alone: a replay walks no nodes)
             run.check(got, ref[k], (name, variant, what))
+            if run.case.f64:
+                for i, (a, want) in enumerate(zip(got["outs"], run.case.f64(k))):
+                    _cmp(a, want.reshape(a.shape), F64_BAR, ((name, variant, what), "output against float64", i))
         assert be.get_stat("graph_replays") - r0 >= 1, "the graph did not replay"
+        print(f"{name}/{key}/{variant}: closest to its bar NMSE {_WORST[0][1]:.2e} (bar {_WORST[0][2]:g})" if _WORST[0][2] else f"{name}/{key}/{variant}: bit-exact")
         return run, k_first
     except BaseException:
         run.close()
         raise
+
+
+LAZY_STATS = ("lazy_conts", "lazy_conts_materialised")
 
 
 # ================================================================================================ the sites
@@ -634,6 +675,232 @@ def _site_decoder(n_tokens):
     return site
 
 
+# ================================================================================================ the sites of graph_exec_t2w.cpp (encoders / Token2Wav)
+# ---- exec_attn_f32 -- K.Q -> SCALE -> SOFT_MAX -> V^T.P -> RESHAPE / PERMUTE -> CONT, all f32, as one attn_f32 launch (guards :107 K.Q, :117 SCALE, :123 SOFT_MAX, :146 the
+# second product, :155 the views in front of the CONT).  The smallest row of test_round5_gpu.py:341 with more than 8 query rows (:111), here with the SCALE node.  Bar 1e-10
+# (test_round5_gpu.py:382), which is also the any-shape f32 GEMM's (test_prefill_kernels_gpu.py:331) that runs the two products node by node; the soft-max rows are compared at
+# the same bar, not at their own 1e-12 (test_prefill_kernels_gpu.py:95): their input is that GEMM's result, as in attn_sm_batch above.
+def site_attn_f32(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+    D, nq, nkv, H = 64, 17, 36, 3
+
+    def build(c):
+        q, k, vt = c.new_tensor(F32, D, nq, H), c.new_tensor(F32, D, nkv, H), c.new_tensor(F32, nkv, D, H)
+        kq = c.mul_mat(k, q)
+        sc = c.scale(kq, 0.125)
+        p = c.soft_max_ext(sc, None, 1.0)
+        o = c.mul_mat(vt, p)
+        out = c.cont(c.permute(c.reshape(o, D, nq, H, 1), 0, 2, 1, 3))
+        return dict(q=q, k=k, vt=vt), dict(kq=(kq, 1e-10), scale=(sc, 1e-10), soft_max=(p, 1e-10), kqv=(o, 1e-10)), [(out, 1e-10)]
+
+    def feeds(rng):
+        return dict(q=rng.standard_normal((H, nq, D)).astype(np.float32), k=rng.standard_normal((H, nkv, D)).astype(np.float32), vt=rng.standard_normal((H, D, nkv)).astype(np.float32))
+    return _simple(pkg, backend, build, feeds)
+
+
+def _ada_chunk(c, ada, C_, B, k):
+    """chunk k of the adaLN product [9C, 1, B]: a [C, 1, B] strided view, one row per batch element"""
+    return c.view_3d(ada, C_, 1, B, ada.nb[1], ada.nb[2], k * C_ * 4)
+
+
+def _layer_norm64(x, eps=1e-5):
+    x = x.astype(np.float64)
+    return (x - x.mean(-1, keepdims=True)) / np.sqrt(x.var(-1, keepdims=True) + eps)
+
+
+# ---- exec_norm_modulate (match_norm_modulate :13 NORM, :24 MUL, :25 the first ADD) -- the DiT's LayerNorm + modulation, norm * scale + norm + shift with [C, 1, B] views, as one
+# norm launch.  The modulated rows carry the OUTPUT flag as in their own test (they are read back, and an element-wise chain must end at them); the gate chain behind them is the
+# second output.  Bar 1e-12 (test_round5_gpu.py:333).
+def site_norm_modulate(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+    C_, T, B = 64, 5, 3
+
+    def build(c):
+        x, ada = c.new_tensor(F32, C_, T, B), c.new_tensor(F32, 9 * C_, 1, B)
+        h = c.norm(x, 1e-5)
+        m = c.mul(h, _ada_chunk(c, ada, C_, B, 1))
+        a1 = c.add(h, m)
+        a2 = c.add(a1, _ada_chunk(c, ada, C_, B, 0))
+        a2.t.flags |= OUTPUT
+        g = c.add(x, c.mul(a2, _ada_chunk(c, ada, C_, B, 2)))
+        return dict(x=x, ada=ada), dict(norm=(h, 1e-12), mul=(m, 1e-12), add1=(a1, 1e-12)), [(a2, 1e-12), (g, 1e-12)]
+
+    def feeds(rng):
+        return dict(x=rng.standard_normal((B, T, C_)).astype(np.float32), ada=rng.standard_normal((B, 1, 9 * C_)).astype(np.float32))
+    return _simple(pkg, backend, build, feeds)
+
+
+# ---- exec_gate_norm (:57 the gate MUL; the chain behind it through match_norm_modulate :13 / :24 / :25) -- the DiT's gated residual x = resid + y * gate in front of the next
+# LayerNorm + modulation: x is computed AND written by the norm launch, so observing x cannot change what is written (output only, as NO_SPLIT's sites).  x has a second reader
+# behind the chain.  Bar 1e-12 against the reference backend (test_round5_gpu.py:333) and, this being the matcher's first test of its own, 1e-10 against a float64 restatement
+# (test_round5_gpu.py:336).
+def site_gate_norm(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+    C_, T, B = 64, 5, 2
+
+    def build(c):
+        y, r, ada = c.new_tensor(F32, C_, T, B), c.new_tensor(F32, C_, T, B), c.new_tensor(F32, 9 * C_, 1, B)
+        gm = c.mul(y, _ada_chunk(c, ada, C_, B, 2))
+        x = c.add(r, gm)
+        h = c.norm(x, 1e-5)
+        m = c.mul(h, _ada_chunk(c, ada, C_, B, 1))
+        a1 = c.add(h, m)
+        a2 = c.add(a1, _ada_chunk(c, ada, C_, B, 0))
+        a2.t.flags |= OUTPUT
+        tail = c.add(x, a2)
+        obs = dict(gate_mul=(gm, 1e-12), norm=(h, 1e-12), mul=(m, 1e-12), add1=(a1, 1e-12), x=(x, 1e-12))
+        return dict(y=y, r=r, ada=ada), obs, [(a2, 1e-12), (tail, 1e-12)]
+
+    def feeds(rng):
+        return dict(y=rng.standard_normal((B, T, C_)).astype(np.float32), r=rng.standard_normal((B, T, C_)).astype(np.float32), ada=rng.standard_normal((B, 1, 9 * C_)).astype(np.float32))
+
+    def f64(f):
+        ada = f["ada"].astype(np.float64)
+        x = f["r"].astype(np.float64) + f["y"].astype(np.float64) * ada[:, :, 2 * C_:3 * C_]
+        h = _layer_norm64(x)
+        a2 = h * ada[:, :, C_:2 * C_] + h + ada[:, :, :C_]
+        return [a2, x + a2]
+    return _simple(pkg, backend, build, feeds, f64=f64)
+
+
+# ---- exec_causal_conv (:557 the CONT of the concatenated frames, :606 the CONT in front of the bias ADD, :619 CONCAT / IM2COL / MUL_MAT / batch CONCAT, :620 the CONT of the
+# transposed x) and, with the layers' caches packed (the cache a strided view of a leaf), lazy_try_register cases A / B (:397, :409): cache_in and cache_tcb are not run, the
+# concat reads the frames in the cache.  token2wav.causal_conv1d_chunk node for node, as test_round5_gpu.py:239 builds it; the new cache goes through exec_concat_tail.  The kernel
+# lies in a WEIGHTS buffer and is written once (its resident rows are made by the eager run).  y is read through the TANH behind the bias ADD.  Bars: 1e-10 for the GEMM and what
+# is computed from it (test_round5_gpu.py:287-289; test_prefill_kernels_gpu.py:331 for the product node by node), copies and the IM2COL gather bit-exact (test_round5_gpu.py:288).
+def _site_causal_conv(packed):
+    def site(pkg, backend):
+        from llama_cpp_omni_amd import token2wav as T2
+        from llama_cpp_omni_amd.ggml import OP
+        F32 = pkg.GGML_TYPE_F32
+        C_, Cout, KW, T, B = 64, 96, 3, 7, 2
+        P, W = KW - 1, 2 * C_ if packed else C_
+
+        def build(c):
+            w, b = c.new_tensor(F32, KW, C_, Cout), c.new_tensor(F32, Cout)
+            x_in, pk = c.new_tensor(F32, C_, T, B), c.new_tensor(F32, W, P, B)
+            x = c.scale(x_in, 1.0)
+            cache = c.view_3d(pk, C_, P, B, pk.nb[1], pk.nb[2], C_ * 4) if packed else pk
+            n0 = len(c.nodes)
+            y, nc = T2.causal_conv1d_chunk(c, x, cache, w, b)
+            act = c.unary(y, pkg.UNARY.TANH)
+            of = lambda op: [t for t in c.nodes[n0:] if t.t.op == op]
+            conts, cats, ims, mms = of(OP.CONT), of(OP.CONCAT), of(OP.IM2COL), of(OP.MUL_MAT)
+            assert (len(conts), len(cats), len(ims), len(mms)) == (8, 3, 2, 2)      # cache_in, cache_tcb, x_tcb, x_cat, y, x_cont, cat, new cache | frames, batch, tail
+            if packed:
+                obs = dict(cache_in=(conts[0], 0), cache_tcb=(conts[1], 0))
+            else:
+                obs = dict(x_t=(conts[2], 0), concat=(cats[0], 0), cont=(conts[3], 0), im2col0=(ims[0], 0), mul_mat1=(mms[1], 1e-10), concat_b=(cats[1], 1e-10), cont_back=(conts[4], 1e-10))
+            return dict(w=w, b=b, x_in=x_in, pk=pk), obs, [(act, 1e-10), (nc, 0)]
+
+        def feeds(rng):
+            return dict(w=(rng.standard_normal((Cout, C_, KW)) / np.sqrt(C_ * KW)).astype(np.float32), b=rng.standard_normal(Cout).astype(np.float32),
+                        x_in=rng.standard_normal((B, T, C_)).astype(np.float32), pk=rng.standard_normal((B, P, W)).astype(np.float32))
+        return _simple(pkg, backend, build, feeds, alloc=dict(usage=pkg.GGML_BACKEND_BUFFER_USAGE_WEIGHTS), once=("w", "b"))
+    return site
+
+
+# ---- exec_concat_tail (:676 the CONT of x, :681 the CONCAT, :689 its CONT) -- the causal convolution's cache shift as one copy of the kept frames out of x, which is itself the
+# output of a copy still queued (test_exec_state_gpu.py:125: its C, P, dt and kept frames).  The matcher compares the VIEW's nb[2] with the copy's (:695), which a 2-D view never
+# meets, so the frames carry a batch dimension (two elements) and the tail is a 3-D view, as token2wav.causal_conv1d_chunk spells it.  The launch count is the copy queue's with
+# or without the matcher, so the control is proved by the concat_tails counter.  x has a second reader behind the tail: without one cont_sink lets x's copy write into CONT(x)'s
+# buffer, the matcher starts at the CONCAT and CONT(x) is written in every case.  Copies and single multiplications: bit-exact.
+def site_concat_tail(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+    C_, P, dt, keep, B = 64, 3, 8, 3, 2
+
+    def build(c):
+        xin, cache = c.new_tensor(F32, dt, C_, B), c.new_tensor(F32, C_, P, B)
+        x = c.cont(c.permute(c.scale(xin, 2.0), 1, 0, 2, 3))
+        n0 = c.cont(x)
+        n1 = c.concat(cache, n0, 1)
+        n2 = c.cont(n1)
+        n3 = c.cont(c.view_3d(n2, C_, keep, B, n2.t.nb[1], n2.t.nb[2], (P + dt - keep) * n2.t.nb[1]))
+        return dict(xin=xin, cache=cache), dict(cont_x=(n0, 0), concat=(n1, 0), cont=(n2, 0)), [(n3, 0), (c.scale(x, 3.0), 0)]
+
+    def feeds(rng):
+        return dict(xin=rng.standard_normal((B, C_, dt)).astype(np.float32), cache=rng.standard_normal((B, P, C_)).astype(np.float32))
+    return _simple(pkg, backend, build, feeds)
+
+
+# ---- exec_conv1d_tc (:730 IM2COL, :744 its CONT, :749 the kernel's CONT, :765 the product, :772 the bias' CONT, :776 the product's CONT, :781 REPEAT) -- the vocoder's 'same'
+# convolution in the reference's spelling, a CONT behind every reshape (test_round5_gpu.py:387, cont=True, its (77, 20, 24, 3, 2) row), as one conv1d_tc launch.  The kernel lies
+# in a WEIGHTS buffer and is written once.  Bars: 1e-10 (test_round5_gpu.py:432; test_prefill_kernels_gpu.py:331 for the product node by node); copies, the zero-padded IM2COL
+# gather and the REPEAT bit-exact.
+def site_conv1d(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+    T, Cin, Cout, KW, dil = 77, 20, 24, 3, 2
+    pad = (KW - 1) * dil // 2
+
+    def build(c):
+        x, w, b = c.new_tensor(F32, T, Cin, 1), c.new_tensor(F32, KW, Cin, Cout), c.new_tensor(F32, Cout)
+        col = c.im2col(w, x, 1, 0, pad, 0, dil, 0, False, F32)
+        col2 = c.cont(c.reshape(col, col.ne[0], col.ne[2] * col.ne[1]))
+        kc = c.cont(c.reshape(w, KW * Cin, Cout))
+        mm = c.mul_mat(col2, kc)
+        y = c.cont(c.reshape(mm, col.ne[1], Cout, col.ne[2]))
+        bc = c.cont(c.reshape(b, 1, Cout, 1))
+        rp = c.repeat(bc, y)
+        out = c.add(y, rp)
+        obs = dict(im2col=(col, 0), col_cont=(col2, 0), kernel_cont=(kc, 0), mul_mat=(mm, 1e-10), prod_cont=(y, 1e-10), bias_cont=(bc, 0), repeat=(rp, 0))
+        return dict(x=x, w=w, b=b), obs, [(out, 1e-10)]
+
+    def feeds(rng):
+        return dict(x=rng.standard_normal((Cin, T)).astype(np.float32), w=(rng.standard_normal((Cout, Cin, KW)) / np.sqrt(Cin * KW)).astype(np.float32), b=rng.standard_normal(Cout).astype(np.float32))
+    return _simple(pkg, backend, build, feeds, alloc=dict(usage=pkg.GGML_BACKEND_BUFFER_USAGE_WEIGHTS), once=("w", "b"))
+
+
+# ---- lazy_try_register cases C / C' (:397) feeding exec_attn_f32 -- the DiT attention as test_t2w_gpu.py:258 spells it: Q, K, V [D, H, T, B] flattened by CONT(PERMUTE), V
+# transposed by a second CONT(PERMUTE); none of the four copies is run, the attention launch reads the permuted views (:138-141, :176) and erases the records (:188-190).  Bars:
+# the copies bit-exact, the merged rows 1e-10 (test_t2w_gpu.py:284).
+def site_lazy_attn(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+    D, H, B, Tq, Tk = 64, 2, 2, 17, 36
+
+    def build(c):
+        q, k, v = c.new_tensor(F32, D, H, Tq, B), c.new_tensor(F32, D, H, Tk, B), c.new_tensor(F32, D, H, Tk, B)
+
+        def flat(t, T):
+            cc = c.cont(c.permute(t, 0, 2, 1, 3))
+            return cc, c.reshape(cc, D, T, H * B)
+        (qc, qf), (kc, kf), (vc, vfl) = flat(q, Tq), flat(k, Tk), flat(v, Tk)
+        vt = c.cont(c.permute(vfl, 1, 0, 2, 3))
+        vf = c.reshape(vt, Tk, D, H * B)
+        probs = c.soft_max_ext(c.scale(c.mul_mat(kf, qf), 1.0 / 8.0), None, 1.0, 0.0)
+        ctx = c.mul_mat(vf, probs)
+        merged = c.cont(c.permute(c.reshape(ctx, D, Tq, H, B), 0, 2, 1, 3))
+        return dict(q=q, k=k, v=v), dict(q_flat=(qc, 0), k_flat=(kc, 0), v_flat=(vc, 0), v_t=(vt, 0)), [(merged, 1e-10)]
+
+    def feeds(rng):
+        return dict(q=rng.standard_normal((B, Tq, H, D)).astype(np.float32), k=rng.standard_normal((B, Tk, H, D)).astype(np.float32), v=rng.standard_normal((B, Tk, H, D)).astype(np.float32))
+    return _simple(pkg, backend, build, feeds)
+
+
+# ---- graph_exec.cpp copy_queue / copy_prune (:867) -- Token2Wav's cache packing in small (test_round6_gpu.py:188, f32): a CONCAT that reads exactly a pending copy's output reads
+# that copy's sources instead, and a pending copy nobody reads any more is never launched.  p3 = CONT(PERMUTE(x3)) is read by the last CONCAT of the pack alone, pack = the first
+# CONCAT of the chain by the second alone: both forwarded and dropped.  The persistent cache is read through the CPY's result (the graph writes only four of its six rows).  Copies,
+# a scale by two and a sum of two equal values: bit-exact (test_round6_gpu.py:238-240).
+def site_copy_prune(pkg, backend):
+    F32 = pkg.GGML_TYPE_F32
+
+    def build(c):
+        x = [c.new_tensor(F32, 8, 5, 3) for _ in range(4)]
+        cache = c.new_tensor(F32, 8, 5, 3, 6)
+        p = [c.cont(c.permute(t, 0, 2, 1, 3)) for t in x]
+        pack1 = c.concat(c.reshape(p[0], 8, 3, 5, 1), c.reshape(p[1], 8, 3, 5, 1), 3)
+        pack = c.concat(pack1, c.reshape(p[2], 8, 3, 5, 1), 3)
+        pack = c.concat(pack, c.reshape(p[3], 8, 3, 5, 1), 3)
+        wide2 = c.concat(c.concat(p[0], p[1], 1), p[2], 1)
+        flat = c.cont(c.permute(pack, 0, 2, 1, 3))
+        stored = c.cpy(flat, c.view_4d(cache, 8, 5, 3, 4, cache.t.nb[1], cache.t.nb[2], cache.t.nb[3], 2 * cache.t.nb[3]))
+        outs = [pack, wide2, stored, c.scale(wide2, 2.0), c.add(c.cont(c.permute(wide2, 0, 2, 1, 3)), c.cont(c.permute(wide2, 0, 2, 1, 3)))]
+        return dict(cache=cache, **{f"x{i}": t for i, t in enumerate(x)}), dict(p3=(p[3], 0), pack=(pack1, 0)), [(o, 0) for o in outs]
+
+    def feeds(rng):
+        return dict(cache=rng.standard_normal((6, 3, 5, 8)).astype(np.float32), **{f"x{i}": rng.standard_normal((3, 5, 8)).astype(np.float32) for i in range(4)})
+    return _simple(pkg, backend, build, feeds)
+
+
 SITES = {   # name: (builder, proof of the control: None = kernels_last_graph below the fusion-off run, or the launch counters of which one must move)
     "unary_f16": (site_unary_f16, None),
     "glu_f16": (site_glu_f16, None),
@@ -657,7 +924,19 @@ SITES = {   # name: (builder, proof of the control: None = kernels_last_graph be
     "attn_sm_batch": (site_attn_sm_batch, None),
     "decode_gs_fold": (_site_decoder(1), ("fattn_gs_launches",)),
     "decode_q8k_image": (_site_decoder(4), None),
+    "attn_f32": (site_attn_f32, None),
+    "norm_modulate": (site_norm_modulate, None),
+    "gate_norm": (site_gate_norm, None),
+    "causal_conv": (_site_causal_conv(False), None),
+    "concat_tail": (site_concat_tail, ("concat_tails",)),
+    "conv1d": (site_conv1d, None),
+    "lazy_cache": (_site_causal_conv(True), ("lazy_conts",)),
+    "lazy_attn": (site_lazy_attn, ("lazy_conts",)),
+    "copy_prune": (site_copy_prune, ("copies_forwarded", "copies_dropped")),
 }
+T2W_SITES = list(SITES)[list(SITES).index("attn_f32"):]
+ALL_MOVE = {"copy_prune"}                                               # (every counter of the proof must move, not one of them)
+LAZY = {"lazy_cache": 2, "lazy_attn": 4}                                # copies the control leaves un-run per graph (test_t2w_gpu.py:252, :281)
 OBS = {
     "unary_f16": ["unary"], "glu_f16": ["glu"], "swiglu_q8k": ["glu"], "soft_max_f16": ["soft_max"], "cont_permute": ["cont"], "cont_sink": ["producer"],
     "ew_chain": ["first", "middle"], "gate_up_swiglu": ["gate", "up", "glu"], "gemm_resid_norm": ["mul_mat"], "gemm_bias_gelu": ["mul_mat", "add", "gelu"],
@@ -665,9 +944,13 @@ OBS = {
     "gemm_any_siblings": ["first", "sibling"], "layer_norm": ["norm", "mul", "add"], "rope_chain_f16": ["mul", "rope"], "rope_chain_store": ["k_mul", "k_rope"],
     "deferred_norm_q8_0": ["norm", "mul"], "deferred_norm_q4_K": ["norm", "mul"], "attn_sm_batch": ["kq", "soft_max", "kqv"], "decode_gs_fold": ["attention"],
     "decode_q8k_image": ["attention"],
+    "attn_f32": ["kq", "scale", "soft_max", "kqv"], "norm_modulate": ["norm", "mul", "add1"], "gate_norm": ["gate_mul", "norm", "mul", "add1", "x"],
+    "causal_conv": ["x_t", "concat", "cont", "im2col0", "mul_mat1", "concat_b", "cont_back"], "concat_tail": ["cont_x", "concat", "cont"],
+    "conv1d": ["im2col", "col_cont", "kernel_cont", "mul_mat", "prod_cont", "bias_cont", "repeat"], "lazy_cache": ["cache_in", "cache_tcb"],
+    "lazy_attn": ["q_flat", "k_flat", "v_flat", "v_t"], "copy_prune": ["p3", "pack"],
 }
-NO_SPLIT = {"swiglu_q8k", "decode_q8k_image"}                           # (these sites write their f32 rows in every case: see the module's docstring)
-OBSERVED = [(s, o, v) for s in SITES for o in OBS[s] for v in ("output", "split") if not (v == "split" and s in NO_SPLIT)]
+NO_SPLIT = {"swiglu_q8k", "decode_q8k_image", ("gate_norm", "x")}       # (these sites / nodes are written in every case: see the module's docstring)
+OBSERVED = [(s, o, v) for s in SITES for o in OBS[s] for v in ("output", "split") if not (v == "split" and (s in NO_SPLIT or (s, o) in NO_SPLIT))]
 
 
 # ================================================================================================ the tests
@@ -692,11 +975,20 @@ def test_control_takes_the_fused_path(pkg, be, ref_be, name):
     assert k_on - 1 < k_off - 8, (k_on, k_off)                          # (without the pad: eight launches with fusion off, one element-wise chain with it)
     if proof:
         assert any(v >= 1 for v in moved.values()), moved
+    if name in ALL_MOVE:
+        assert all(v >= 1 for v in moved.values()), moved
+    if name in LAZY:
+        assert run.moved["lazy_conts"] == LAZY[name] and run.moved["lazy_conts_materialised"] == 0, run.moved
 
 
 @pytest.mark.parametrize("name,key,variant", OBSERVED, ids=[f"{s}-{o}-{v}" for s, o, v in OBSERVED])
 def test_interior_node_is_written_for_a_reader_outside_the_split(pkg, be, ref_be, name, key, variant):
-    run, _ = _three_runs(pkg, be, ref_be, name, key, variant)
+    run, k_first = _three_runs(pkg, be, ref_be, name, key, variant)
+    if name in LAZY:                                                    # an observed lazy copy became real: it was not left un-run, and it was launched or made real later
+        k_control = _control_launches(pkg, be, name)
+        print(f"{name}/{key}/{variant}: {k_first} launches ({k_control} in the control), {run.moved}")
+        assert run.moved["lazy_conts"] < LAZY[name], run.moved
+        assert k_first > k_control or run.moved["lazy_conts_materialised"] >= 1, (k_first, k_control, run.moved)
     if variant == "split":                                              # the counts say what the test means them to say: one more use than the split holds
         parent, (first, second) = run.graph(True)
         inside = sum(1 for T in run.nodes[:run.cut] for k in range(10) if T.t.src[k] and _same(T.t.src[k], run.t))
@@ -709,7 +1001,24 @@ def _same(p, T):
     return ctypes.addressof(p.contents) == ctypes.addressof(T.t)
 
 
-VIEWED = [("cont_permute", "cont"), ("soft_max_f16", "soft_max"), ("ew_chain", "middle"), ("layer_norm", "add"), ("stream_encoder", "v_cast")]
+_CONTROL = {}
+
+
+def _control_launches(pkg, be, name):
+    """kernels_last_graph of the site's control, eager (once per site)"""
+    if name not in _CONTROL:
+        _fresh(be)
+        run = Run(pkg, be, name)
+        try:
+            run.submit(0)
+            _CONTROL[name] = run.kernels
+        finally:
+            run.close()
+    return _CONTROL[name]
+
+
+VIEWED = [("cont_permute", "cont"), ("soft_max_f16", "soft_max"), ("ew_chain", "middle"), ("layer_norm", "add"), ("stream_encoder", "v_cast"),
+          ("attn_f32", "soft_max"), ("causal_conv", "cont"), ("conv1d", "prod_cont"), ("lazy_attn", "k_flat"), ("copy_prune", "pack")]
 
 
 @pytest.mark.parametrize("where", ["split_view", "split_view_front"])
@@ -728,7 +1037,7 @@ def test_interior_node_read_through_a_view_node_only(pkg, be, ref_be, name, key,
     run.close()
 
 
-CROWDED = [("soft_max_f16", "soft_max"), ("cont_sink", "producer"), ("gemm_any_bias_gelu", "add")]
+CROWDED = [("soft_max_f16", "soft_max"), ("cont_sink", "producer"), ("gemm_any_bias_gelu", "add"), ("lazy_attn", "q_flat"), ("causal_conv", "im2col0")]
 
 
 @pytest.mark.parametrize("name,key", CROWDED, ids=[f"{s}-{o}" for s, o in CROWDED])
@@ -743,7 +1052,8 @@ def test_interior_node_displaced_in_a_tight_parent_table(pkg, be, ref_be, name, 
 
 
 FLIPS = [("soft_max_f16", "soft_max"), ("unary_f16", "unary"), ("cont_sink", "producer"), ("ew_chain", "middle"), ("gemm_any_bias_gelu", "add"), ("layer_norm", "mul"),
-         ("rope_chain_store", "k_rope"), ("attn_sm_batch", "soft_max")]
+         ("rope_chain_store", "k_rope"), ("attn_sm_batch", "soft_max"),
+         ("attn_f32", "soft_max"), ("gate_norm", "gate_mul"), ("causal_conv", "cont"), ("lazy_attn", "v_t"), ("concat_tail", "concat"), ("copy_prune", "pack")]
 
 
 @pytest.mark.parametrize("name,key", FLIPS, ids=[f"{s}-{o}" for s, o in FLIPS])
@@ -752,6 +1062,7 @@ def test_capture_is_not_replayed_once_the_interior_node_has_an_outside_reader(pk
     (same nodes, same data pointers, same fingerprint: only recs_match's `ext` tells them apart), three times; then the control's graph again with the OUTPUT flag set
     (recs_match's `flags`).  The interior node is poisoned before each run and must be written every time it is observed."""
     ref = _reference(pkg, ref_be, name)
+    _fresh(be)
     run = Run(pkg, be, name, key, "split")
     try:
         r0 = be.get_stat("graph_replays")
@@ -770,5 +1081,10 @@ def test_capture_is_not_replayed_once_the_interior_node_has_an_outside_reader(pk
         run.t.t.flags &= ~OUTPUT
         run.check(run.submit(0, with_reader=False, observed=False), ref[0], (name, "control again"))
         assert run.kernels == k_control, (run.kernels, k_control)
+        if name in T2W_SITES:                                           # ... and the control is captured and replayed again (a copy dropped or left lazy in it is dropped again)
+            r1 = be.get_stat("graph_replays")
+            for k in (1, 2):
+                run.check(run.submit(k, with_reader=False, observed=False), ref[k], (name, "control again", k))
+            assert be.get_stat("graph_replays") - r1 >= 1 and run.kernels == k_control, (be.get_stat("graph_replays") - r1, run.kernels, k_control)
     finally:
         run.close()
