@@ -56,6 +56,8 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * the prefill GEMM, process-wide), "norm_in_kernel" (0/1 RMS_NORM+MUL built inside the consuming decode mat-vec launches; default 0),
  * "fattn_gqa" (0/1 matrix-core kernel for few-token FLASH_ATTN_EXT; 0 = streaming kernel for every such shape; default 1, process-wide),
  * "fattn_dma" (-1 default / 0 / 1: the LDS-DMA ring form of the prefill attention kernel for head size 128 on large grids, process-wide),
+ * "fattn_wide" (-1 default (on) / 0 / 1: the matrix-core FLASH_ATTN_EXT kernel for head sizes 256 / 256 and 576 / 512 over an F16 cache, csrc/kernels/fattn_wide.hip;
+ * 0 sends those shapes to the generic one-wave-per-row kernel: the cross-check switch; process-wide, drops captured graphs),
  * "prefill_q8k" (0 default / 1: the prefill GEMMs of K-quant weights take the Q8_K-QUANTISED activations -- the reference CPU backend's vec_dot_type
  * arithmetic, ggml-cpu.c:1245-1268 -- instead of plain f16 rows; process-wide), "mmq_tile" (0 default / 1: Q4_K weights x more than 64 columns on the int8
  * matrix cores from the blocks, csrc/kernels/mmq_tile.hip: the oracle's exact integer sums, slower than the F16-image GEMM; process-wide),
@@ -71,6 +73,7 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * MI355X_LOG_STATS, MI355X_GRAPH_GPU_TIME, MI355X_LAUNCH_LOG=file, MI355X_GRAPH_SLICE="nodes:lo:hi,..." (instrumentation, see tools/t2w_slices.sh). */
 GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const char * key, long value);
 /* counters: "graph_replays", "graph_captures", "eager_graphs", "kernels_last_graph", "mmq_tile_launches",
+ * "fattn_wide_launches" (launches of the head-size 256 / 576 attention kernel, csrc/kernels/fattn_wide.hip; the merge pass of a sliced node is not counted),
  * "mmv_iq4nl_launches", "mmv_iq4xs_launches", "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches" (launches of the
  * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
  * "argsort_launches", "ssm_conv_launches" / "ssm_scan_launches" (SSM_CONV / SSM_SCAN: one launch per node),

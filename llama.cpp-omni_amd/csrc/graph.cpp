@@ -365,6 +365,7 @@ int mi355x_set_option(struct ggml_backend * backend, const char * key, long valu
     if (!strcmp(key, "copy_batch")) { c->opt_copy_batch = (int) value; mi::drop_graph_execs(c); return 0; }
     if (!strcmp(key, "fattn_gs")) { mi::fattn_set_gs((int) value); mi::drop_graph_execs(c); return 0; }       // (process-wide)
     if (!strcmp(key, "fattn_dma")) { mi::fattn_set_dma((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide)
+    if (!strcmp(key, "fattn_wide")) { mi::fattn_set_wide((int) value); mi::drop_graph_execs(c); return 0; }    // (process-wide)
     if (!strcmp(key, "f16_shadow")) { mi::shadow_set_enabled(value != 0); mi::drop_graph_execs(c); return 0; }
     if (!strcmp(key, "reset_stats")) { c->prof.clear(); c->stat_replays = c->stat_captures = c->stat_eager = 0; return 0; }
     return -1;
@@ -394,6 +395,7 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mv2_cus"))            return (double) mi::mv2_cus_of(c->device);
     if (!strcmp(key, "gemm_kq_launches"))   return (double) mi::gemm_variant_launches(3);
     if (!strcmp(key, "fattn_dma_launches")) return (double) mi::fattn_dma_launches();
+    if (!strcmp(key, "fattn_wide_launches")) return (double) mi::fattn_wide_launches();
     if (!strcmp(key, "attn_vrows_launches")) return (double) mi::attn_vrows_launches();
     if (!strcmp(key, "fattn_gs_launches"))  return (double) mi::fattn_gs_launches();
     if (!strcmp(key, "fattn_gs_far_launches")) return (double) mi::fattn_gs_far_launches();

@@ -831,6 +831,10 @@ void exec_fattn(exec_state & s, int i) {
     fattn_args f; tdesc m;
     fill_fattn_args(n, f, m);
     if ((n->src[0]->ne[0] != 64 && n->src[0]->ne[0] != 128) || n->src[2]->ne[0] != n->src[0]->ne[0] || n->src[1]->type != GGML_TYPE_F16) {      // other head sizes / cache types: the generic kernel, no fused stage
+        if (fattn_wide_takes(f) && fattn_scratch_bytes(f) > 0) {      // head sizes 256 / 576 over a deep cache: workspace of the KV slices (+ the merge launch)
+            f.scratch = fa_scratch_take(s, FA_KV_SPLIT, n); f.scratch_bytes = s.c->fa_scratch_bytes;
+            ++s.n_kernels;
+        }
         prof_scope ps(s, "fattn", 0);
         flash_attn_ext_f16(f, s.st); ++s.n_kernels;
         note_write(s, n);

@@ -427,6 +427,45 @@ static gqa_plan fa_gqa_plan(const fattn_args & f) {
     return p;
 }
 
+// Head sizes 256 / 256 (Gemma 2 / 3) and 576 / 512 (DeepSeek MLA) over an F16 cache: k_fattn_wide (fattn_wide.hip).  The single place that decides
+// whether that kernel takes a node, in how many KV slices and with how many waves: consulted by the dispatch below, by fattn_scratch_bytes and through
+// fattn_wide_takes by the executor.  Everything it refuses stays on the generic kernel (fattn_any.hip).
+// Slices: up to FA_WIDE_DIRECT_TILES = 16 tiles of 32 rows (n_kv <= 512) one workgroup per column-tile group walks the whole range and finishes its rows: one
+// launch, no scratch.  Above that, when the grid without a split is below 512 workgroups, the range is cut into slices of >= 4 tiles (at most 128 slices) and
+// k_fattn_merge folds the partial rows.
+static int g_wide_mode = -1;
+void fattn_set_wide(int m) { g_wide_mode = m; }
+constexpr int FA_WIDE_DIRECT_TILES = 16;
+struct wide_plan { bool ok; int nsplit, nw; };
+static wide_plan fa_wide_plan(const fattn_args & f) {
+    static const bool off = getenv("MI355X_FA_NO_WIDE") != nullptr;
+    wide_plan p = { false, 1, 4 };
+    if (g_wide_mode == 0 || (g_wide_mode < 0 && off)) return p;
+    if (f.v_transposed || f.kv_type != GGML_TYPE_F16 || !fattn_wide_dims(f.q.ne[0], f.v.ne[0]) || f.k.ne[0] != f.q.ne[0]) return p;
+    if (f.max_bias != 0.0f || f.pre || f.img || f.out16) return p;
+    if (f.mask && f.mask->ne[2] != 1) return p;                       // (a per-head mask would need per-lane mask rows)
+    const int64_t nq = f.q.ne[1], nh = f.q.ne[2], nhkv = f.k.ne[2], nkv = f.k.ne[1], ns = f.q.ne[3];
+    if (nq < 1 || nh < 1 || nhkv < 1 || nkv < 1 || ns < 1 || nh % nhkv != 0 || f.v.ne[1] != nkv || f.v.ne[2] != nhkv) return p;
+    const int64_t ntile = (nkv + 31) / 32;
+    if (ntile > fattn_wide_max_tiles() || nq * nh * ns > (int64_t) 1 << 30) return p;
+    // the kernel's vector loads: 16-byte rows and bases of Q (f32x4), K and V (8 halfs); the f32 output rows are stored as f32x4
+    auto al16 = [](const tdesc & t) { return ((uintptr_t) t.p | t.nb[1] | t.nb[2] | t.nb[3]) % 16 == 0; };
+    if (!al16(f.q) || !al16(f.k) || !al16(f.v) || !al16(f.dst) || f.q.nb[0] != 4 || f.k.nb[0] != 2 || f.v.nb[0] != 2 || f.dst.nb[0] != 4) return p;
+    if (f.mask && (f.mask->nb[0] != 2 || f.mask->ne[0] < nkv || f.mask->ne[1] < nq)) return p;
+    p.ok = true;
+    if (ntile > FA_WIDE_DIRECT_TILES) {
+        const int64_t gq = nh / nhkv, ctw = f.v.ne[0] > 256 ? 2 : 4;                                  // column tiles per workgroup (fattn_wide.hip)
+        const int64_t nct = gq >= 32 ? nq * ((gq + 31) / 32) : (nq + 32 / gq - 1) / (32 / gq);
+        const int64_t wgs = (nct + ctw - 1) / ctw * nhkv * ns;
+        int64_t s = 512 / wgs;
+        if (s > ntile / 4) s = ntile / 4;
+        if (s > 128) s = 128;
+        if (s >= 2) { const int64_t tps = (ntile + s - 1) / s; p.nsplit = (int) ((ntile + tps - 1) / tps); }     // (no empty slice)
+    }
+    return p;
+}
+bool fattn_wide_takes(const fattn_args & f) { return fa_wide_plan(f).ok; }
+
 template <int D, int R, int NW>
 static size_t fa_lds_bytes() { return (size_t) R * D * 4 + NW * 16 * R * 4 + NW * R * (D + 2) * 4; }
 
@@ -448,6 +487,8 @@ bool fattn_sm_prefill_ok(const fattn_args & f) {
 size_t fattn_map_bytes(int64_t nq, int64_t nkv, int64_t mne2, int64_t mne3);
 size_t fattn_map_bytes_host(int64_t nq, int64_t nkv) { return fattn_map_bytes(nq, nkv, 1, 1); }
 size_t fattn_scratch_bytes(const fattn_args & f) {
+    if (const wide_plan wp = fa_wide_plan(f); wp.ok)                  // partial (O, M, S) rows of the slices: columns x slices x (DV + 2) floats
+        return wp.nsplit > 1 ? (size_t) (f.q.ne[1] * f.q.ne[2] * f.q.ne[3]) * (size_t) wp.nsplit * (size_t) (f.v.ne[0] + 2) * 4 : 0;
     if (!fa_use_mma(f)) {                                             // decode kernels: partial rows of the KV split
         fattn_args g = f; g.pre = nullptr;
         const gqa_plan gp = fa_gqa_plan(g);
@@ -542,6 +583,19 @@ void flash_attn_ext_f16(const fattn_args & f, hipStream_t st) {
         const fattn_pre & p = *f.pre;
         a.pre = { (const char *) p.qraw, p.q_hs, (const char *) p.kraw, p.k_hs, (const char *) p.vraw, p.v_hs, p.qw, p.kw, p.pos, p.ff, p.eps, make_rope_dev(p.rp),
                   (char *) p.kcache, p.kc_rs, (char *) p.vcache, p.vc_rs, (const char *) p.kidx, (const char *) p.vidx, p.idx_is64 };
+    }
+    if (const wide_plan wp = fa_wide_plan(f); wp.ok) {                // head sizes 256 / 256 and 576 / 512, F16 cache: the matrix-core kernel of fattn_wide.hip
+        const int DV = (int) f.v.ne[0];
+        a.nsplit = 1; a.part = nullptr; a.tile_map = nullptr; a.map_nqb = 0;
+        if (wp.nsplit > 1 && f.scratch && f.scratch_bytes >= fattn_scratch_bytes(f)) { a.nsplit = wp.nsplit; a.part = (float *) f.scratch; }   // (no workspace: one slice, still correct)
+        flash_attn_ext_wide(a, (int) f.q.ne[0], DV, st);
+        if (a.nsplit > 1) {
+            const int nblk = (int) ((a.nh * DV + 255) / 256);
+            const dim3 grid((unsigned) (a.nq * a.ns * nblk));
+            if (DV == 256) k_fattn_merge<256><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
+            else           k_fattn_merge<512><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
+        }
+        return;
     }
     if (!f.v_transposed && ((f.q.ne[0] != 64 && f.q.ne[0] != 128) || f.v.ne[0] != f.q.ne[0] || f.kv_type != GGML_TYPE_F16)) {     // other head sizes / cache types: the generic kernel (no pre-stage, no images)
         if (f.pre || f.img || f.out16 || !fattn_any_ok(f.q.ne[0], f.v.ne[0])) { fprintf(stderr, "[mi355x] flash_attn: head size %d / %d with a fused stage\n", (int) f.q.ne[0], (int) f.v.ne[0]); abort(); }
