@@ -42,6 +42,7 @@ static inline rope_params rope_params_of(const ggml_tensor * r) {
     rp.n_dims = op_param_i32(r, 1); rp.mode = op_param_i32(r, 2); rp.n_ctx_orig = op_param_i32(r, 4);
     rp.freq_base = op_param_f32(r, 5); rp.freq_scale = op_param_f32(r, 6); rp.ext_factor = op_param_f32(r, 7);
     rp.attn_factor = op_param_f32(r, 8); rp.beta_fast = op_param_f32(r, 9); rp.beta_slow = op_param_f32(r, 10);
+    if (rope_is_mrope(rp.mode)) for (int k = 0; k < 4; ++k) rp.sections[k] = op_param_i32(r, 11 + k);      // (ggml_rope_multi; rope_ext nodes: zeros)
     return rp;
 }
 static inline tdesc swapped01(tdesc d) { std::swap(d.ne[0], d.ne[1]); std::swap(d.nb[0], d.nb[1]); return d; }

@@ -561,6 +561,7 @@ bool match_norm_rope(exec_state & s, int j, nr_chain & c) {
     ggml_tensor * r = g->nodes[ri];
     const int mode = op_param_i32(r, 2);
     const ggml_tensor * pos = r->src[1], * ff = r->src[2];
+    // (modes 8 / 24 -- M-RoPE, vision -- stay with the plain op: no architecture of the reference puts a norm in front of them)
     if (!((mode == GGML_ROPE_TYPE_NORMAL || mode == GGML_ROPE_TYPE_NEOX) && op_param_i32(r, 1) == D && r->nb[0] == 4 && pos && pos->type == GGML_TYPE_I32 &&
           pos->nb[0] == 4 && (!ff || (ff->type == GGML_TYPE_F32 && ff->nb[0] == 4)))) return false;
     c.norm = j; c.mul = mi_; c.rope = ri; c.store = -1; c.wt = wt; c.pos = pos; c.ff = ff; c.xin = n->src[0]; c.first = j;
@@ -934,8 +935,10 @@ bool match_rope_only(exec_state & s, int j, nr_chain & c) {
     const int64_t D = r->ne[0];
     const int mode = op_param_i32(r, 2);
     if (!x || x->type != GGML_TYPE_F32 || r->type != GGML_TYPE_F32 || x->nb[0] != 4 || r->nb[0] != 4 || D % 2 != 0 || D > 256 || r->ne[3] != 1 || !same_shape(x, r)) return false;
-    if (!((mode == GGML_ROPE_TYPE_NORMAL || mode == GGML_ROPE_TYPE_NEOX) && op_param_i32(r, 1) == D && pos && pos->type == GGML_TYPE_I32 && pos->nb[0] == 4 &&
+    // M-RoPE (mode 8: llm_build_qwen2vl) rides along as the NEOX rotation from a table, or inline angles, that read the four position rows by section; vision mode never
+    if (!((mode == GGML_ROPE_TYPE_NORMAL || mode == GGML_ROPE_TYPE_NEOX || mode == GGML_ROPE_TYPE_MROPE) && op_param_i32(r, 1) == D && pos && pos->type == GGML_TYPE_I32 && pos->nb[0] == 4 &&
           (!ff || (ff->type == GGML_TYPE_F32 && ff->nb[0] == 4)))) return false;
+    if (mode == GGML_ROPE_TYPE_MROPE && (pos->ne[0] < 4 * r->ne[2] || op_param_i32(r, 11) + op_param_i32(r, 12) + op_param_i32(r, 13) + op_param_i32(r, 14) <= 0)) return false;
     c.norm = -1; c.mul = -1; c.rope = j; c.store = -1; c.wt = nullptr; c.pos = pos; c.ff = ff; c.xin = x; c.first = j;
     c.D = (int) D; c.H = (int) r->ne[1]; c.T = (int) r->ne[2]; c.eps = 0.0f;
     c.rp = rope_params_of(r);

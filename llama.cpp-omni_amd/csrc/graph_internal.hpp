@@ -65,14 +65,14 @@ struct act_cache {
     void seed(const ggml_tensor * x, act_kind k) { src = x->data; kind = k; K = x->ne[0]; from = range_of(x); for (int d = 0; d < 3; ++d) { ne[d] = x->ne[d + 1]; nb[d] = x->nb[d + 1]; } }
     void drop() { src = nullptr; }      void invalidate(byte_range w) { if (src && overlap(w, from)) drop(); }
 };
-// rt -- in rope_scratch: the (cos, sin) table of T positions x D / 2 pairs.  Set by remember(): ensure_rope_table (the one-token attention launches) and the prefill
+// rt -- in rope_scratch: the (cos, sin) table of T positions x D / 2 pairs (the key rp holds an M-RoPE node's sections).  Set by remember(): ensure_rope_table (the one-token attention launches) and the prefill
 //   norm + rope launch, which fills the table itself when told it is not valid.  Consumed by the same (every layer of a graph shares it).  Ended by a write into the
 //   positions or frequency factors read.
 struct rope_cache {
     const void * pos = nullptr; const void * ff = nullptr; int T = 0, D = 0; rope_params rp; byte_range from_pos = { nullptr, nullptr }, from_ff = { nullptr, nullptr };
     bool holds(const void * p, const void * f, int T_, int D_, const rope_params & r) const { return pos && pos == p && ff == f && T == T_ && D == D_ && memcmp(&rp, &r, sizeof(rope_params)) == 0; }
-    void remember(const void * p, const void * f, int T_, int D_, const rope_params & r) {      // T positions and D / 2 frequency factors were read
-        pos = p; ff = f; T = T_; D = D_; rp = r; from_pos = { (const char *) p, (const char *) p + (size_t) T_ * 4 }; from_ff = { (const char *) f, f ? (const char *) f + (size_t) (D_ / 2) * 4 : nullptr };
+    void remember(const void * p, const void * f, int T_, int D_, const rope_params & r) {      // T positions (M-RoPE: four rows of T) and D / 2 frequency factors were read
+        pos = p; ff = f; T = T_; D = D_; rp = r; from_pos = { (const char *) p, (const char *) p + (size_t) T_ * 4 * (rope_is_mrope(r.mode) ? 4 : 1) }; from_ff = { (const char *) f, f ? (const char *) f + (size_t) (D_ / 2) * 4 : nullptr };
     }
     void drop() { pos = nullptr; }      void invalidate(byte_range w) { if (pos && (overlap(w, from_pos) || overlap(w, from_ff))) drop(); }
 };

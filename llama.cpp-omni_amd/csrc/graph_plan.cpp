@@ -166,9 +166,16 @@ bool supports_op(const ggml_tensor * op) {
         case GGML_OP_ROPE: {
             if (!s0 || !s1 || s0->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || s1->type != GGML_TYPE_I32) return false;
             const int mode = op_param_i32(op, 2);
-            if (mode != GGML_ROPE_TYPE_NORMAL && mode != GGML_ROPE_TYPE_NEOX) return false;     // mrope / vision: CPU
+            const int n_dims = op_param_i32(op, 1);
             if (op->src[2] && op->src[2]->type != GGML_TYPE_F32) return false;
-            return s0->nb[0] == 4 && op->nb[0] == 4 && (op_param_i32(op, 1) % 2) == 0;
+            if (mode == GGML_ROPE_TYPE_MROPE || mode == GGML_ROPE_TYPE_VISION) {                // ggml_rope_multi (Qwen2-VL text layers, and its ViT): four rows of positions, sections in op_params[11..14]
+                const int sc[4] = { op_param_i32(op, 11), op_param_i32(op, 12), op_param_i32(op, 13), op_param_i32(op, 14) };
+                if (sc[0] < 0 || sc[1] < 0 || sc[2] < 0 || sc[3] < 0 || !(sc[0] > 0 || sc[1] > 0 || sc[2] > 0)) return false;       // (the reference asserts a positive t, h or w section ...
+                if ((int64_t) sc[0] + sc[1] + sc[2] + sc[3] > s0->ne[0] || s1->ne[0] < 4 * s0->ne[2] || s1->nb[0] != 4) return false;     //  ... and sect_dims <= ne0)
+                if (n_dims <= 0 || n_dims > s0->ne[0] || (mode == GGML_ROPE_TYPE_VISION && n_dims != s0->ne[0] / 2)) return false;
+                if (op->src[2] && op->src[2]->ne[0] < (mode == GGML_ROPE_TYPE_VISION ? n_dims : n_dims / 2)) return false;           // one factor per rotated pair
+            } else if (mode != GGML_ROPE_TYPE_NORMAL && mode != GGML_ROPE_TYPE_NEOX) return false;                                    // every other mode value: CPU.  So are F16 rotation and ROPE_BACK
+            return s0->nb[0] == 4 && op->nb[0] == 4 && (n_dims % 2) == 0;
         }
         case GGML_OP_SOFT_MAX:
             if (!s0 || s0->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32 || !is_contiguous(op) || s0->nb[0] != 4) return false;

@@ -212,11 +212,18 @@ long norm_from_split_launches();
 bool norm_rows_from_split_ok(const tdesc & x, const tdesc & y, int nsplit, size_t resid_cs, size_t resid2_cs, const void * resid, const void * resid2, const void * part);
 void norm_rows_from_split(const tdesc & x, const tdesc & y, float eps, const float * w, const float * b, uint16_t * y16, size_t y16_rs, bool write_f32,
                           const float * part, int nsplit, size_t split_elems, const float * resid, size_t resid_cs, const float * resid2, size_t resid2_cs, hipStream_t st);   // x = split-K slabs + addends, written, then the LayerNorm
-// ROPE f32 (ops.cpp:5534-5720): modes NORMAL / NEOX, optional freq factors, YaRN
+// ROPE f32 (ops.cpp:5534-5720): modes NORMAL / NEOX / MROPE (8) / VISION (24), optional freq factors, YaRN
+// MROPE / VISION: pos holds four rows of ne2 positions (t, h, w, e); sections[] says which row each rotation pair reads (zeros for rope_ext nodes)
 struct rope_params {
     int   n_dims, mode, n_ctx_orig;
     float freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow;
+    int   sections[4];
 };
+// the ONE spelling of the three mode questions, for host and device code alike (no site tests a mode bit itself)
+__host__ __device__ static inline bool rope_is_mrope(int mode)  { return (mode & GGML_ROPE_TYPE_MROPE) != 0; }      // four position rows + sections: modes 8 and 24
+__host__ __device__ static inline bool rope_is_vision(int mode) { return mode == GGML_ROPE_TYPE_VISION; }
+// pairs (p, p + n_dims / 2): NEOX, and M-RoPE whose mode value has the NEOX bit clear (vision pairs (p, p + n_dims) are no NEOX pairs: only k_rope rotates them)
+__host__ __device__ static inline bool rope_pairs_neox(int mode) { return (mode & GGML_ROPE_TYPE_NEOX) != 0 || mode == GGML_ROPE_TYPE_MROPE; }
 void rope_f32(const tdesc & x, const int32_t * pos, const float * freq_factors, const tdesc & y, const rope_params & rp, hipStream_t st);
 // SOFT_MAX (ops.cpp:5072-5182): y = softmax(x*scale + slope*mask)
 void soft_max_f32(const tdesc & x, const tdesc * mask, int mask_type, const float * sinks, const tdesc & y, float scale, float max_bias, hipStream_t st,

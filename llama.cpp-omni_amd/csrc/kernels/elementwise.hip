@@ -3,6 +3,7 @@
 // (ggml/src/ggml-cpu/ops.cpp); the line ranges are cited per kernel.
 #include "../kernels.hpp"
 #include "act_dev.hpp"
+#include "norm_rope_dev.hpp"
 #include <float.h>
 
 namespace mi {
@@ -590,46 +591,27 @@ void norm_f32(const tdesc & x, const tdesc & y, float eps, hipStream_t st) {
 // (theta_0 = pos; theta_{i+1} = theta_i * theta_scale) so the angle is bit-identical; only cosf/sinf
 // differ (device libm vs glibc, <= 2 ulp).
 // ================================================================================================
-struct rope_dev_e {
-    int   n_dims, mode;
-    float theta_scale, freq_scale, ext_factor, attn_factor, corr0, corr1;
-};
-
-__global__ void __launch_bounds__(256) k_rope(td4 x, td4 y, const int32_t * __restrict__ pos, const float * __restrict__ ff, rope_dev_e rp) {
+// MROPE (8): four position rows, the row chosen per pair by its section (mrope_row), NEOX pairs.  VISION (24): n_dims == ne0 / 2, every pair p < n_dims rotates
+// (p, p + n_dims) and the thetas restart at each section.  Frequency factors are read for rotated pairs only.
+__global__ void __launch_bounds__(256) k_rope(td4 x, td4 y, const int32_t * __restrict__ pos, const float * __restrict__ ff, int n_dims, rope_dev rd) {
     // grid: (ne1 heads, ne2 tokens, ne3); threads over pairs
     const int64_t i1 = blockIdx.x, i2 = blockIdx.y, i3 = blockIdx.z;
     const char * xr = x.p + i1 * x.nb[1] + i2 * x.nb[2] + i3 * x.nb[3];
     char *       yr = y.p + i1 * y.nb[1] + i2 * y.nb[2] + i3 * y.nb[3];
-    const int ne0 = (int) x.ne[0];
-    const bool neox = rp.mode & GGML_ROPE_TYPE_NEOX;
-    const float p = (float) pos[i2];
+    const int ne0 = (int) x.ne[0], T = (int) x.ne[2];
+    const bool vision = rope_is_vision(rd.mode);
+    const bool neox = rope_pairs_neox(rd.mode);
+    const int nrot = vision ? n_dims : n_dims / 2;                          // rotated pairs
     for (int ip = threadIdx.x; ip < ne0 / 2; ip += blockDim.x) {
         const int i0 = 2 * ip;
-        if (i0 < rp.n_dims) {
-            float theta = p;
-            for (int k = 0; k < ip; ++k) theta *= rp.theta_scale;          // sequential, as ggml_rope_cache_init
-            const float f = ff ? ff[ip] : 1.0f;
-            const float theta_extrap = theta / f;
-            float theta_interp = rp.freq_scale * theta_extrap;
-            float th = theta_interp, mscale = rp.attn_factor;
-            if (rp.ext_factor != 0.0f) {
-                const float yv = ((float) (i0 / 2) - rp.corr0) / fmaxf(0.001f, rp.corr1 - rp.corr0);
-                const float ramp_mix = (1.0f - fminf(1.0f, fmaxf(0.0f, yv))) * rp.ext_factor;
-                th = theta_interp * (1.0f - ramp_mix) + theta_extrap * ramp_mix;
-                mscale *= 1.0f + 0.1f * logf(1.0f / rp.freq_scale);
-            }
-            const float c = cosf(th) * mscale, s = sinf(th) * mscale;
-            if (neox) {
-                const float x0 = *(const float *) (xr + (int64_t) ip * x.nb[0]);
-                const float x1 = *(const float *) (xr + (int64_t) (ip + rp.n_dims / 2) * x.nb[0]);
-                *(float *) (yr + (int64_t) ip * y.nb[0])                   = x0 * c - x1 * s;
-                *(float *) (yr + (int64_t) (ip + rp.n_dims / 2) * y.nb[0]) = x0 * s + x1 * c;
-            } else {
-                const float x0 = *(const float *) (xr + (int64_t) i0 * x.nb[0]);
-                const float x1 = *(const float *) (xr + (int64_t) (i0 + 1) * x.nb[0]);
-                *(float *) (yr + (int64_t) i0 * y.nb[0])       = x0 * c - x1 * s;
-                *(float *) (yr + (int64_t) (i0 + 1) * y.nb[0]) = x0 * s + x1 * c;
-            }
+        if (ip < nrot) {
+            float c, s;
+            rope_angle_tok(pos, (int) i2, T, ip, ff, rd, c, s);                // theta by sequential products, as ggml_rope_cache_init
+            const int e0 = neox || vision ? ip : i0, e1 = vision ? ip + n_dims : neox ? ip + n_dims / 2 : i0 + 1;      // vision: (p, p + n_dims)
+            const float x0 = *(const float *) (xr + (int64_t) e0 * x.nb[0]);
+            const float x1 = *(const float *) (xr + (int64_t) e1 * x.nb[0]);
+            *(float *) (yr + (int64_t) e0 * y.nb[0]) = x0 * c - x1 * s;
+            *(float *) (yr + (int64_t) e1 * y.nb[0]) = x0 * s + x1 * c;
         } else {                                   // pass-through channels beyond n_dims
             *(float *) (yr + (int64_t) i0 * y.nb[0])       = *(const float *) (xr + (int64_t) i0 * x.nb[0]);
             *(float *) (yr + (int64_t) (i0 + 1) * y.nb[0]) = *(const float *) (xr + (int64_t) (i0 + 1) * x.nb[0]);
@@ -637,22 +619,13 @@ __global__ void __launch_bounds__(256) k_rope(td4 x, td4 y, const int32_t * __re
     }
 }
 
-// ggml_rope_yarn_corr_dim / _dims (ggml.c): restated on the host
-static float rope_corr_dim(int n_dims, int n_ctx_orig, float n_rot, float base) {
-    return n_dims * logf(n_ctx_orig / (n_rot * 2 * (float) M_PI)) / (2 * logf(base));
-}
-
 void rope_f32(const tdesc & x, const int32_t * pos, const float * ff, const tdesc & y, const rope_params & rp, hipStream_t st) {
     if (x.ne[0] * x.ne[1] * x.ne[2] * x.ne[3] == 0) return;
-    rope_dev_e d;
-    d.n_dims = rp.n_dims; d.mode = rp.mode;
-    d.theta_scale = powf(rp.freq_base, -2.0f / rp.n_dims);
-    d.freq_scale = rp.freq_scale; d.ext_factor = rp.ext_factor; d.attn_factor = rp.attn_factor;
-    const float start = floorf(rope_corr_dim(rp.n_dims, rp.n_ctx_orig, rp.beta_fast, rp.freq_base));
-    const float end   = ceilf (rope_corr_dim(rp.n_dims, rp.n_ctx_orig, rp.beta_slow, rp.freq_base));
-    d.corr0 = fmaxf(0.0f, start); d.corr1 = fminf((float) rp.n_dims - 1, end);
+    if (rope_is_mrope(rp.mode) && (rp.sections[0] + rp.sections[1] + rp.sections[2] + rp.sections[3] <= 0 || (rope_is_vision(rp.mode) && rp.n_dims * 2 != x.ne[0]))) {
+        fprintf(stderr, "[mi355x] rope_f32: mode %d with sections (%d, %d, %d, %d), n_dims %d, ne0 %lld\n", rp.mode, rp.sections[0], rp.sections[1], rp.sections[2], rp.sections[3], rp.n_dims, (long long) x.ne[0]); abort();
+    }
     dim3 grid((unsigned) x.ne[1], (unsigned) x.ne[2], (unsigned) x.ne[3]);
-    k_rope<<<grid, dim3(64), 0, st>>>(to_td4(x), to_td4(y), pos, ff, d);
+    k_rope<<<grid, dim3(64), 0, st>>>(to_td4(x), to_td4(y), pos, ff, rp.n_dims, make_rope_dev(rp));
 }
 
 // ================================================================================================

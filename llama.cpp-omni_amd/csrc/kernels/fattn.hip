@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(64 * NW) k_fattn_dec(const fa_dev a) {
                 const int  hq  = ikv * a.gq + hc * a.hpw + (isk ? 0 : r);
                 const char * xr = isk ? P.kraw + ikv * P.k_hs : P.qraw + hq * P.q_hs;
                 float r0[1], r1[1]; int e0[1], e1[1]; bool act[1];
-                norm_rope_wave<1>(xr, isk ? P.kw : P.qw, D, P.eps, posf, P.ff, P.rd, lane, r0, r1, e0, e1, act);
+                norm_rope_wave<1>(xr, isk ? P.kw : P.qw, D, P.eps, posf, P.ff, P.rd, lane, r0, r1, e0, e1, act, nullptr, P.pos);
                 if (act[0]) {
                     if (isk) {
                         const int64_t row = P.idx_is64 ? *(const int64_t *) P.kidx : (int64_t) *(const int32_t *) P.kidx;

@@ -975,7 +975,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)
                 const int  r   = task - 2;
                 const char * xr = isk ? P.kraw + ikv * P.k_hs : P.qraw + (ikv * a.gq + r) * P.q_hs;
                 float r0[1], r1[1]; int e0[1], e1[1]; bool act[1];
-                norm_rope_wave<1>(xr, isk ? P.kw : P.qw, D, P.eps, posf, P.ff, P.rd, lane, r0, r1, e0, e1, act);
+                norm_rope_wave<1>(xr, isk ? P.kw : P.qw, D, P.eps, posf, P.ff, P.rd, lane, r0, r1, e0, e1, act, nullptr, P.pos);
                 if (act[0]) {
                     if (isk) {
                         uint16_t * kr = (uint16_t *) (P.kcache + krow * P.kc_rs) + ikv * D;

@@ -846,7 +846,7 @@ void flash_attn_one(const fa_dev & f, int D, const float * rope_tab, hipStream_t
     a.k = f.k; a.v = f.v; a.mask = f.mask; a.sinks = f.sinks; a.dst = f.dst;
     a.q_hs = (int) P.q_hs; a.k_hs = (int) P.k_hs; a.v_hs = (int) P.v_hs; a.kc_rs = (int) P.kc_rs; a.vc_rs = (int) P.vc_rs;
     a.knb1 = (int) f.knb1; a.knb2 = (int) f.knb2; a.vnb1 = (int) f.vnb1; a.vnb2 = (int) f.vnb2; a.mnb2 = (int) f.mnb2; a.mne2 = (int) f.mne2; a.dnb1 = (int) f.dnb1;
-    a.nkv = f.nkv; a.gq = f.gq; a.neox = (P.rd.mode & GGML_ROPE_TYPE_NEOX) ? 1 : 0; a.n_head_log2 = (int) f.n_head_log2;
+    a.nkv = f.nkv; a.gq = f.gq; a.neox = rope_pairs_neox(P.rd.mode) ? 1 : 0; a.n_head_log2 = (int) f.n_head_log2;
     a.has_norm = P.qw != nullptr; a.vidx_st = 0; a.vidx_n = 0;
     a.nsplit = f.nsplit > 1 ? f.nsplit : 1; a.part = f.part; a.cnt = f.nsplit > 1 ? f.cnt : nullptr;
     a.eps = P.eps; a.scale = f.scale; a.max_bias = f.max_bias; a.logit_softcap = f.logit_softcap; a.m0 = f.m0; a.m1 = f.m1;
@@ -898,7 +898,7 @@ void flash_attn_gs(const fa_dev & f, int D, const float * rope_tab, float * part
     a.k = f.k; a.v = f.v; a.mask = f.mask; a.sinks = nullptr; a.dst = f.dst;
     a.q_hs = (int) P.q_hs; a.k_hs = (int) P.k_hs; a.v_hs = (int) P.v_hs; a.kc_rs = (int) P.kc_rs; a.vc_rs = (int) P.vc_rs;
     a.knb1 = (int) f.knb1; a.knb2 = (int) f.knb2; a.vnb1 = (int) f.vnb1; a.vnb2 = (int) f.vnb2; a.mnb2 = (int) f.mnb2; a.mne2 = (int) f.mne2; a.dnb1 = (int) f.dnb1;
-    a.nkv = f.nkv; a.gq = f.gq; a.neox = (P.rd.mode & GGML_ROPE_TYPE_NEOX) ? 1 : 0; a.n_head_log2 = (int) f.n_head_log2;
+    a.nkv = f.nkv; a.gq = f.gq; a.neox = rope_pairs_neox(P.rd.mode) ? 1 : 0; a.n_head_log2 = (int) f.n_head_log2;
     a.has_norm = P.qw != nullptr; a.nsplit = FGS_NSL; a.part = parts; a.cnt = nullptr;
     a.eps = P.eps; a.scale = f.scale; a.max_bias = 0.0f; a.logit_softcap = 0.0f; a.m0 = 1.0f; a.m1 = 1.0f;
     a.n_head = f.nh; a.nkvh_log2 = -1;
@@ -960,7 +960,7 @@ void attn_one_sm(const attn_sm_args & f, hipStream_t st) {
     a.k = (const char *) f.k; a.v = (const char *) f.v; a.mask = (const char *) f.mask; a.sinks = nullptr; a.dst = (char *) f.dst;
     a.q_hs = (int) P.q_hs; a.k_hs = (int) P.k_hs; a.v_hs = (int) P.v_hs; a.kc_rs = (int) P.kc_rs; a.vc_rs = 2;
     a.knb1 = (int) f.knb1; a.knb2 = (int) f.knb2; a.vnb1 = (int) f.vnb1; a.vnb2 = (int) f.vnb2; a.mnb2 = (int) f.mnb2; a.mne2 = (int) (f.mne2 > 0 ? f.mne2 : 1); a.dnb1 = (int) f.dnb1;
-    a.nkv = f.nkv; a.gq = f.n_head / f.n_head_kv; a.neox = (P.rp.mode & GGML_ROPE_TYPE_NEOX) ? 1 : 0; a.n_head_log2 = 0;
+    a.nkv = f.nkv; a.gq = f.n_head / f.n_head_kv; a.neox = rope_pairs_neox(P.rp.mode) ? 1 : 0; a.n_head_log2 = 0;
     const int nsplit = (f.nkv + FA1_NKV - 1) / FA1_NKV;
     a.vidx_st = P.idx_is64 ? 8 : 4; a.vidx_n = (int) f.vidx_n; a.has_norm = P.qw != nullptr; a.nsplit = nsplit; a.part = nsplit > 1 ? (float *) f.part : nullptr; a.cnt = nsplit > 1 ? f.counters : nullptr;
     a.eps = P.eps; a.scale = f.scale; a.max_bias = 0.0f; a.logit_softcap = 0.0f; a.m0 = 1.0f; a.m1 = 1.0f;

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) k_rope_table(const int32_t * __restrict__
     if (i >= T * half) return;
     const int t = i / half, ip = i - t * half;
     float c, s;
-    rope_angle((float) pos[t], ip, ff, rd, c, s);
+    rope_angle_tok(pos, t, T, ip, ff, rd, c, s);
     tab[2 * i] = c; tab[2 * i + 1] = s;
 }
 
@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) k_norm_rope(const nr_dev a) {
     }
 
     float r0[PPL], r1[PPL]; int e0[PPL], e1[PPL]; bool act[PPL];
-    norm_rope_wave<PPL>(xr, J.w, a.D, a.eps, (float) a.pos[t], a.ff, a.rd, lane, r0, r1, e0, e1, act, a.tab ? a.tab + (size_t) t * a.D : nullptr);
+    norm_rope_wave<PPL>(xr, J.w, a.D, a.eps, (float) a.pos[t], a.ff, a.rd, lane, r0, r1, e0, e1, act, a.tab ? a.tab + (size_t) t * a.D : nullptr, a.pos, t, a.T);
 #pragma unroll
     for (int q = 0; q < PPL; ++q) {
         if (!act[q]) continue;
@@ -158,7 +158,7 @@ long norm_rope_split_launches() { return g_norm_rope_split_launches; }
 // would norm_rope_store run the kernel that can sum split-K slabs (k_norm_rope_v4), for these jobs?  (the same test as below, on the host arguments)
 bool norm_rope_takes_split(const norm_rope_args & f) {
     static const bool off = getenv("MI355X_NO_NORM_ROPE_V4") != nullptr;
-    if (off || f.D != 128 || f.T < 16 || !(f.rp.mode & GGML_ROPE_TYPE_NEOX) || !f.rope_tab || f.njobs <= 0) return false;
+    if (off || f.D != 128 || f.T < 16 || !rope_pairs_neox(f.rp.mode) || !f.rope_tab || f.njobs <= 0) return false;
     for (int i = 0; i < f.njobs; ++i) {
         const norm_rope_job & d = f.j[i];
         const bool plain = !d.w && !d.rope_only;
@@ -190,7 +190,7 @@ void norm_rope_store(const norm_rope_args & f, hipStream_t st) {
     }
     {   // many tokens, D = 128, NEOX, table angles, 16-byte aligned rows, heads in fours: the 16-lanes-per-row kernel
         static const bool off = getenv("MI355X_NO_NORM_ROPE_V4") != nullptr;
-        bool v4 = !off && f.D == 128 && f.T >= 16 && (a.rd.mode & GGML_ROPE_TYPE_NEOX) && a.tab != nullptr;
+        bool v4 = !off && f.D == 128 && f.T >= 16 && rope_pairs_neox(a.rd.mode) && a.tab != nullptr;
         for (int i = 0; i < f.njobs && v4; ++i) {
             const nr_job & d = a.j[i];
             v4 = d.H % 4 == 0 && ((uintptr_t) d.x & 15) == 0 && d.xnb1 % 16 == 0 && d.xnb2 % 16 == 0 && (!d.w || ((uintptr_t) d.w & 15) == 0) &&

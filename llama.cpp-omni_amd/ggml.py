@@ -12,7 +12,7 @@ import numpy as np
 __all__ = [
     "lib_path", "load_library", "Backend", "backend", "Context", "Tensor",
     "GGML_TYPE_F32", "GGML_TYPE_F16", "GGML_TYPE_Q8_0", "GGML_TYPE_Q4_K", "GGML_TYPE_Q6_K", "GGML_TYPE_I32", "GGML_TYPE_I64",
-    "GGML_BACKEND_BUFFER_USAGE_ANY", "GGML_BACKEND_BUFFER_USAGE_WEIGHTS", "GGML_BACKEND_BUFFER_USAGE_COMPUTE", "GGML_ROPE_TYPE_NORMAL", "GGML_ROPE_TYPE_NEOX", "type_traits", "row_size", "OP", "GLU", "UNARY", "SORT_ORDER", "ggml_tensor", "ggml_cgraph", "ggml_hash_size", "Graph",
+    "GGML_BACKEND_BUFFER_USAGE_ANY", "GGML_BACKEND_BUFFER_USAGE_WEIGHTS", "GGML_BACKEND_BUFFER_USAGE_COMPUTE", "GGML_ROPE_TYPE_NORMAL", "GGML_ROPE_TYPE_NEOX", "GGML_ROPE_TYPE_MROPE", "GGML_ROPE_TYPE_VISION", "type_traits", "row_size", "OP", "GLU", "UNARY", "SORT_ORDER", "ggml_tensor", "ggml_cgraph", "ggml_hash_size", "Graph",
 ]
 
 # ------------------------------------------------------------------------------------------------ constants
@@ -22,6 +22,7 @@ GGML_TYPE_I32, GGML_TYPE_I64 = 26, 27
 GGML_TYPE_IQ4_NL, GGML_TYPE_IQ4_XS = 20, 23
 GGML_TYPE_MXFP4 = 39                      # {uint8 e (E8M0); uint8 qs[16]}: 32 weights in 17 bytes (ggml-common.h block_mxfp4)
 GGML_ROPE_TYPE_NORMAL, GGML_ROPE_TYPE_NEOX = 0, 2
+GGML_ROPE_TYPE_MROPE, GGML_ROPE_TYPE_VISION = 8, 24      # ggml_rope_multi: four position rows and sections[4]
 GGML_PREC_F32 = 10
 GGML_BACKEND_BUFFER_USAGE_ANY, GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_BACKEND_BUFFER_USAGE_COMPUTE = 0, 1, 2   # ggml-backend.h:49-53
 
@@ -933,6 +934,17 @@ class Context:
     def rope_ext(self, a, pos, freq_factors, n_dims, mode, n_ctx_orig, freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow):
         T = self._new(a.type, a.ne)
         params = [0, n_dims, mode, 0, n_ctx_orig] + [_f32_bits(x) for x in (freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow)] + [0, 0, 0, 0]
+        return self._op(T, OP.ROPE, [a, pos, freq_factors], params)
+
+    def rope_multi(self, a, pos, freq_factors, n_dims, sections, mode, n_ctx_orig, freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow, inplace=False):
+        """ggml_rope_multi (inplace: ggml_rope_multi_inplace, the result a view of a): pos holds four rows of a.ne[2] positions (t, h, w, e); the layout is
+        rope_ext's with sections[4] in op_params[11..14]"""
+        assert a.ne[2] * 4 == pos.ne[0] and len(sections) == 4 and mode & 1 == 0
+        T = self._new(a.type, a.ne, view_src=a if inplace else None)
+        if inplace:
+            for i in range(4):
+                T.t.nb[i] = a.t.nb[i]
+        params = [0, n_dims, mode, 0, n_ctx_orig] + [_f32_bits(x) for x in (freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow)] + [int(s) for s in sections]
         return self._op(T, OP.ROPE, [a, pos, freq_factors], params)
 
     def soft_max_ext(self, a, mask, scale, max_bias=0.0):

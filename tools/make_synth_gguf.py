@@ -166,8 +166,9 @@ def quant_q8_0(x):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", choices=["8b", "tiny", "tts", "tts-tiny"], default="8b",
-                    help="8b / tiny: qwen3 arch; tts / tts-tiny: the omni TTS decoder's shape (arch llama, RoPE NORM, no q/k-norm; SURVEY.md 8(f) rank 2)")
+    ap.add_argument("--config", choices=["8b", "tiny", "tts", "tts-tiny", "qwen2vl-tiny"], default="8b",
+                    help="8b / tiny: qwen3 arch; tts / tts-tiny: the omni TTS decoder's shape (arch llama, RoPE NORM, no q/k-norm; SURVEY.md 8(f) rank 2); "
+                         "qwen2vl-tiny: arch qwen2vl (no q/k-norm, attn_q/k/v.bias, M-RoPE with qwen2vl.rope.dimension_sections)")
     ap.add_argument("--types", choices=["q4_k_m", "f16", "q8_0", "q4_0", "q5_k", "iq4_xs", "iq4_nl", "q4_1", "q5_1", "q2_k", "q3_k"], default="q4_k_m")
     ap.add_argument("-o", "--out", required=True)
     ap.add_argument("--seed", type=int, default=1234)
@@ -190,8 +191,12 @@ def main():
     from llama_cpp_omni_amd.ggml import GGML_TYPE_F16, GGML_TYPE_F32, GGML_TYPE_Q4_K, GGML_TYPE_Q8_0, row_size
     TTS = dict(n_embd=768, n_layer=20, n_head=12, n_head_kv=12, head_dim=64, n_ff=3072, n_vocab=32000, rms_eps=1e-6, rope_base=1e4, n_ctx_orig=4096)
     TTS_TINY = dict(n_embd=256, n_layer=2, n_head=4, n_head_kv=4, head_dim=64, n_ff=512, n_vocab=512, rms_eps=1e-6, rope_base=1e4, n_ctx_orig=4096)
+    # llm_build_qwen2vl: wq is [n_embd, n_embd] (n_head * head_dim == n_embd); the sections sum to head_dim / 2, split as Qwen2-VL's 16 / 24 / 24 of 64
+    QWEN2VL_TINY = dict(n_embd=256, n_layer=2, n_head=4, n_head_kv=2, head_dim=64, n_ff=512, n_vocab=512, rms_eps=1e-6, rope_base=1e6, n_ctx_orig=4096,
+                        rope_sections=(8, 12, 12, 0))
     is_llama = args.config.startswith("tts")
-    cfg = {"8b": qwen3.QWEN3_8B, "tiny": qwen3.TINY, "tts": TTS, "tts-tiny": TTS_TINY}[args.config]
+    is_q2vl = args.config == "qwen2vl-tiny"
+    cfg = {"8b": qwen3.QWEN3_8B, "tiny": qwen3.TINY, "tts": TTS, "tts-tiny": TTS_TINY, "qwen2vl-tiny": QWEN2VL_TINY}[args.config]
     if args.layers:
         cfg = dict(cfg, n_layer=args.layers)
     if args.types == "q4_k_m":
@@ -228,7 +233,9 @@ def main():
         tensors += [(f"blk.{il}.attn_norm.weight", GGML_TYPE_F32, (E,)), (f"blk.{il}.attn_q.weight", t["attn_q"], (E, H * D)),
                     (f"blk.{il}.attn_k.weight", t["attn_k"], (E, HK * D)), (f"blk.{il}.attn_v.weight", t["attn_v"], (E, HK * D)),
                     (f"blk.{il}.attn_output.weight", t["attn_output"], (H * D, E))]
-        if not is_llama:
+        if is_q2vl:
+            tensors += [(f"blk.{il}.attn_q.bias", GGML_TYPE_F32, (H * D,)), (f"blk.{il}.attn_k.bias", GGML_TYPE_F32, (HK * D,)), (f"blk.{il}.attn_v.bias", GGML_TYPE_F32, (HK * D,))]
+        elif not is_llama:
             tensors += [(f"blk.{il}.attn_q_norm.weight", GGML_TYPE_F32, (D,)), (f"blk.{il}.attn_k_norm.weight", GGML_TYPE_F32, (D,))]
         tensors += [(f"blk.{il}.ffn_norm.weight", GGML_TYPE_F32, (E,)),
                     (f"blk.{il}.ffn_gate.weight", t["ffn_gate"], (E, F)), (f"blk.{il}.ffn_up.weight", t["ffn_up"], (E, F)),
@@ -238,7 +245,7 @@ def main():
         rows = int(np.prod(ne[1:])) if len(ne) > 1 else 1
         return row_size(ty, ne[0]) * rows
 
-    arch = "llama" if is_llama else "qwen3"
+    arch = "llama" if is_llama else "qwen2vl" if is_q2vl else "qwen3"
     kvs = [kv_str("general.architecture", arch), kv_str("general.name", f"qwen3-{args.config}-{args.types}-synthetic"), kv_u32("general.file_type", ftype),
            kv_u32("general.quantization_version", 2), kv_u32("general.alignment", ALIGN),
            kv_u32(f"{arch}.block_count", L), kv_u32(f"{arch}.context_length", args.n_ctx), kv_u32(f"{arch}.embedding_length", E),
@@ -249,6 +256,9 @@ def main():
     kvs += omni_vocab_kvs(V) if args.vocab == "omni" else [kv_str("tokenizer.ggml.model", "no_vocab")]
     if is_llama:
         kvs.append(kv_u32(f"{arch}.rope.dimension_count", D))
+    if is_q2vl:
+        assert H * D == E and sum(cfg["rope_sections"]) == D // 2
+        kvs.append(kv_arr_i32(f"{arch}.rope.dimension_sections", cfg["rope_sections"]))
 
     offs, off = [], 0
     for _, ty, ne in tensors:
@@ -263,6 +273,8 @@ def main():
     cache = {}
 
     def data_for(name, ty, ne):
+        if name.endswith(".bias"):
+            return (0.1 * rng.standard_normal(ne[0])).astype(np.float32).view(np.uint8)
         if ty == GGML_TYPE_F32 and len(ne) == 1:
             return np.ones(ne[0], np.float32).view(np.uint8)
         base = name.split(".", 2)[2] if name.startswith("blk.") else name
