@@ -67,6 +67,20 @@ static void make_recs(backend_ctx * c, const ggml_cgraph * g, graph_exec & e) {
         r.direct = it == direct.end() ? 0 : it->second;
         r.ext = e.with_ext ? (whole_use_count(g, n) > r.direct ? 1 : 0) : 0;
     }
+    // sources outside the node list: type, shape and strides (graph.hpp leaf_rec).  ne[4] and nb[4] lie side by side in ggml_tensor, as in the record.
+    e.leafs.clear();
+    std::unordered_map<const ggml_tensor *, int> is_node;
+    is_node.reserve((size_t) g->n_nodes * 2);
+    for (int i = 0; i < g->n_nodes; ++i) is_node[g->nodes[i]] = i;
+    for (int i = 0; i < g->n_nodes; ++i)
+        for (int k = 0; k < GGML_MAX_SRC; ++k) {
+            const ggml_tensor * sr = g->nodes[i]->src[k];
+            if (!sr || is_node.count(sr)) continue;
+            leaf_rec l; memset(&l, 0, sizeof l);
+            l.node = i; l.slot = k; l.type = (uint32_t) sr->type;
+            for (int d = 0; d < 4; ++d) { l.ne[d] = sr->ne[d]; l.nb[d] = sr->nb[d]; }
+            e.leafs.push_back(l);
+        }
 }
 // does the submitted cgraph equal what capture e was built from?  (the hot path of a decode step: ~1200 nodes, a handful of compares each)
 static bool recs_match(backend_ctx * c, const ggml_cgraph * g, const graph_exec & e) {
@@ -79,8 +93,13 @@ static bool recs_match(backend_ctx * c, const ggml_cgraph * g, const graph_exec 
         if (memcmp(r.ne, n->ne, sizeof r.ne) != 0 || memcmp(r.nb, n->nb, sizeof r.nb) != 0 || memcmp(r.op_params, n->op_params, sizeof r.op_params) != 0) return false;
         for (int k = 0; k < GGML_MAX_SRC; ++k) if (r.src[k] != (n->src[k] ? n->src[k]->data : nullptr)) return false;
     }
-    // (the source SHAPES need no compare of their own: a source is a node of this graph -- compared above -- or a leaf, whose shape cannot change
-    //  under an unchanged node that reads it; the reference compares the same set of fields)
+    // a source is a node of this graph -- compared above -- or lies outside it: then its type, shape and strides are compared here.  (They CAN change under an unchanged
+    // node that reads it: MUL_MAT's result says nothing about the type or the row stride of its weights, and a released buffer's addresses come back.  The slots were
+    // non-null at capture time and the pointer compare above holds, so they are non-null now.)
+    for (const leaf_rec & l : e.leafs) {
+        const ggml_tensor * sr = g->nodes[l.node]->src[l.slot];
+        if (!sr || l.type != (uint32_t) sr->type || memcmp(l.ne, sr->ne, sizeof l.ne) != 0 || memcmp(l.nb, sr->nb, sizeof l.nb) != 0) return false;
+    }
     if (e.with_ext)
         for (int i = 0; i < g->n_nodes; ++i) {
             const node_rec & r = e.recs[(size_t) i];
@@ -204,7 +223,7 @@ enum ggml_status graph_compute(backend_ctx * c, ggml_cgraph * g) {
         }
         if (ge->exec && !recs_match(c, g, *ge)) {                  // same fingerprint, different graph (a collision, or other readers outside the cgraph): never replay it
             HIP_CHECK(hipGraphExecDestroy(ge->exec)); HIP_CHECK(hipGraphDestroy(ge->graph));
-            ge->exec = nullptr; ge->graph = nullptr; ge->seen = 1; ge->recs.clear();
+            ge->exec = nullptr; ge->graph = nullptr; ge->seen = 1; ge->recs.clear(); ge->leafs.clear();
             c->stat_fp_mismatch++;
         }
         if (ge->exec) {

@@ -19,6 +19,10 @@ struct node_rec {
     const void * data; uint32_t op, type; int32_t flags; int32_t ext;
     int64_t ne[4]; size_t nb[4]; int32_t op_params[GGML_MAX_OP_PARAMS / 4]; const void * src[GGML_MAX_SRC]; int32_t direct, pad;
 };
+// ... and the sources that are NOT nodes of the cgraph (leaves: weights, inputs, caches; nodes of an earlier split): the node records hold their data pointers only, and
+// a leaf of another type or with other strides can lie at the same address under field-for-field equal nodes -- in a new buffer that got a released one's addresses, or
+// re-laid-out by the allocator inside a live one.  One record per (node, source slot), compared behind the node records.
+struct leaf_rec { int32_t node, slot; uint32_t type, pad; int64_t ne[4]; size_t nb[4]; };
 struct graph_exec {                    // one captured cgraph
     uint64_t        fingerprint = 0;   // (bookkeeping of graphs seen but not yet captured; identity of a capture is `recs`)
     int             seen = 0;          // times this fingerprint was submitted
@@ -29,6 +33,7 @@ struct graph_exec {                    // one captured cgraph
     uint64_t        shadow_gen = 0;    // shadow_generation() at capture time
     bool            with_ext = false;  // recs[].ext was derived from use_counts (the graph carried them and fusion was on)
     std::vector<node_rec> recs;
+    std::vector<leaf_rec> leafs;
 };
 
 struct backend_ctx {

@@ -24,7 +24,9 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
         ++s.n_kernels;
     };
     prof_scope ps(s, "act_convert", 0);
-    const bool flat = (ne12 == 1 || x->nb[2] == (size_t) N * x->nb[1]) && (ne13 == 1 || x->nb[3] == (size_t) ne12 * x->nb[2]);
+    // rows nb[1] apart from the first to the last one: slice i13 starts ne12 * N rows behind slice i13 - 1  (nb[2] says nothing when ne12 == 1: measured against nb[2], a src1 of
+    // ne12 == 1, ne13 > 1 whose slices lie further apart -- the first N of N + 3 rows -- passed for flat and the rows between the slices were converted as activations)
+    const bool flat = (ne12 == 1 || x->nb[2] == (size_t) N * x->nb[1]) && (ne13 == 1 || x->nb[3] == (size_t) (ne12 * N) * x->nb[1]);
     if (x->type == GGML_TYPE_F16) {
         // F16 x F16 (the MUL_MAT of ggml_conv_1d / ggml_conv_2d: im2col columns against an f16 kernel): the activation rows are already
         // in the GEMM's format; gather them into the dense image (supports_op admits F16 src1 only next to F16 src0)

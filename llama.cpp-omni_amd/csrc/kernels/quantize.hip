@@ -142,8 +142,12 @@ __global__ void __launch_bounds__(256) k_quantize_q81(const char * __restrict__ 
     char * im = img + row * img_bytes;
     ((int8_t *) im)[ib * 32 + l] = (int8_t) q;
     if (l == 0) {
+        // the reference rounds twice: the f32 product, then that to f16.  Left to the compiler, product and conversion become one v_fma_mixlo_f16 -- the exact product rounded
+        // once -- which lands on the other f16 wherever the f32 product is an exact f16 tie (one block in ~10^4): keep the f32 value a value of its own
+        float s = d * (float) sum;
+        asm volatile("" : "+v"(s));
         ((float *) (im + K))[ib]      = h2f(f2h(d));
-        ((float *) (im + K))[nb + ib] = h2f(f2h(d * (float) sum));
+        ((float *) (im + K))[nb + ib] = h2f(f2h(s));
     }
 }
 
