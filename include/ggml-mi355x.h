@@ -62,7 +62,7 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * arithmetic, ggml-cpu.c:1245-1268 -- instead of plain f16 rows; process-wide), "mmq_tile" (0 default / 1: Q4_K weights x more than 64 columns on the int8
  * matrix cores from the blocks, csrc/kernels/mmq_tile.hip: the oracle's exact integer sums, slower than the F16-image GEMM; process-wide),
  * "mmq_id" (1 default / 0: MUL_MAT_ID of Q4_K / Q5_K / Q6_K experts from 64 tokens on, of MXFP4 experts from 128 and of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts from 65 tokens on, runs on the
- * expert-grouped int8-MFMA kernels, csrc/kernels/mmq_id.hip / mmq_id_mxfp4.hip / mmq_id_blocks.hip -- the pairs sorted by expert on the device, one tile per (expert, 32 rows, <= 32 columns); 0 sends every node
+ * expert-grouped int8-MFMA kernels, csrc/kernels/mmq_id.hip -- the pairs sorted by expert on the device, one tile per (expert, 32 rows, <= 32 columns); 0 sends every node
  * to the per-pair mat-vec: the cross-check switch; process-wide),
  * "mv1", "mv2", "fattn_one", "kq_staging", "batch_uploads" (cross-check switches of the decode kernels),
  * "reset_stats".  Returns 0 on success, -1 for an unknown key.

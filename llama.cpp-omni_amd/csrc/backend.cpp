@@ -231,10 +231,10 @@ static void be_free(ggml_backend_t b) {
     if (getenv("MI355X_LOG_STATS"))
         log_msg(GGML_LOG_LEVEL_INFO, "[mi355x] %s: graphs eager=%ld captured=%ld replayed=%ld, kernels in last graph=%ld\n", c->name.c_str(),
                 c->stat_eager, c->stat_captures, c->stat_replays, c->stat_kernels_last);
-    if (getenv("MI355X_LOG_STATS") && (mmv_id_launches() || argsort_launches() || mmv_id_mxfp4_launches() || add_id_launches() || mmq_id_launches() || mmq_id_mxfp4_launches() ||
-                                       mmv_id_blocks_launches() || mmq_id_blocks_launches()))
+    const long mmq_id_kq = mmq_id_stats(MMQ_ID_KQUANT).launches, mmq_id_mx = mmq_id_stats(MMQ_ID_MXFP4).launches, mmq_id_bl = mmq_id_stats(MMQ_ID_BLOCKS).launches;
+    if (getenv("MI355X_LOG_STATS") && (mmv_id_launches() || argsort_launches() || mmv_id_mxfp4_launches() || add_id_launches() || mmq_id_kq || mmq_id_mx || mmv_id_blocks_launches() || mmq_id_bl))
         log_msg(GGML_LOG_LEVEL_INFO, "[mi355x] mixture-of-experts launches (process-wide): mmv_id=%ld argsort=%ld mmv_id_mxfp4=%ld add_id=%ld mmq_id=%ld mmq_id_mxfp4=%ld mmv_id_blocks=%ld mmq_id_blocks=%ld\n",
-                mmv_id_launches(), argsort_launches(), mmv_id_mxfp4_launches(), add_id_launches(), mmq_id_launches(), mmq_id_mxfp4_launches(), mmv_id_blocks_launches(), mmq_id_blocks_launches());
+                mmv_id_launches(), argsort_launches(), mmv_id_mxfp4_launches(), add_id_launches(), mmq_id_kq, mmq_id_mx, mmv_id_blocks_launches(), mmq_id_bl);
     if (getenv("MI355X_LOG_STATS") && (ssm_conv_launches() || ssm_scan_launches()))
         log_msg(GGML_LOG_LEVEL_INFO, "[mi355x] state-space launches (process-wide): ssm_conv=%ld ssm_scan=%ld\n", ssm_conv_launches(), ssm_scan_launches());
     if (getenv("MI355X_LOG_STATS") && (wkv6_launches() || gla_launches() || wkv7_launches() || l2_norm_launches()))

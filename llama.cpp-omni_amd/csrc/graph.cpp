@@ -376,7 +376,7 @@ int mi355x_set_option(struct ggml_backend * backend, const char * key, long valu
     if (!strcmp(key, "fp_collide")) { mi::g_fp_collide = value != 0; return 0; }
     if (!strcmp(key, "prefill_q8k")) { mi::prefill_q8k_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: prefill GEMMs of K-quant weights take the Q8_K-quantised activations; 0 = plain f16 rows, the round-4 arithmetic)
     if (!strcmp(key, "mmq_tile")) { mi::mmq_tile_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: the tiled int8-MFMA prefill kernel for Q4_K weights, mmq_tile.hip; 0 = the F16-image GEMM)
-    if (!strcmp(key, "mmq_id")) { mi::mmq_id_set_mode(value != 0); mi::drop_graph_execs(c); return 0; }      // (process-wide: MUL_MAT_ID of K-quant experts from 64 tokens of MXFP4 experts from 128 and of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts from 65 tokens on the expert-grouped int8-MFMA kernels, mmq_id.hip / mmq_id_mxfp4.hip / mmq_id_blocks.hip; 0 = the per-pair mat-vec at every token count)
+    if (!strcmp(key, "mmq_id")) { mi::mmq_id_set_mode(value != 0); mi::drop_graph_execs(c); return 0; }      // (process-wide: MUL_MAT_ID of K-quant experts from 64 tokens of MXFP4 experts from 128 and of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts from 65 tokens on the expert-grouped int8-MFMA kernels, mmq_id.hip; 0 = the per-pair mat-vec at every token count)
     if (!strcmp(key, "mv2")) { mi::mmv2_enable(value != 0); mi::drop_graph_execs(c); return 0; }       // (process-wide: the LDS-DMA engine form of the decode mat-vec)
     if (!strcmp(key, "kq_staging")) { c->opt_kq_staging = value != 0; mi::drop_graph_execs(c); return 0; }
     if (!strcmp(key, "fattn_gqa")) { mi::fattn_set_gqa(value != 0); mi::drop_graph_execs(c); return 0; }
@@ -425,10 +425,10 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmv_q2k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q2_K);
     if (!strcmp(key, "mmv_q3k_launches"))   return (double) mi::mmv_blocks_launches(mi::MMV_FORM_Q3_K);
     if (!strcmp(key, "mmv_id_launches"))    return (double) mi::mmv_id_launches();
-    if (!strcmp(key, "mmq_id_launches"))    return (double) mi::mmq_id_launches();
-    if (!strcmp(key, "mmq_id_ks"))          return (double) mi::mmq_id_last_ks();
-    if (!strcmp(key, "mmq_id_mxfp4_launches")) return (double) mi::mmq_id_mxfp4_launches();
-    if (!strcmp(key, "mmq_id_mxfp4_ks"))    return (double) mi::mmq_id_mxfp4_last_ks();
+    if (!strcmp(key, "mmq_id_launches"))    return (double) mi::mmq_id_stats(mi::MMQ_ID_KQUANT).launches;
+    if (!strcmp(key, "mmq_id_ks"))          return (double) mi::mmq_id_stats(mi::MMQ_ID_KQUANT).ks;
+    if (!strcmp(key, "mmq_id_mxfp4_launches")) return (double) mi::mmq_id_stats(mi::MMQ_ID_MXFP4).launches;
+    if (!strcmp(key, "mmq_id_mxfp4_ks"))    return (double) mi::mmq_id_stats(mi::MMQ_ID_MXFP4).ks;
     if (!strcmp(key, "argsort_launches"))   return (double) mi::argsort_launches();
     if (!strcmp(key, "ssm_conv_launches"))  return (double) mi::ssm_conv_launches();
     if (!strcmp(key, "ssm_scan_launches"))  return (double) mi::ssm_scan_launches();
@@ -439,8 +439,8 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "mmv_id_mxfp4_launches")) return (double) mi::mmv_id_mxfp4_launches();
     if (!strcmp(key, "add_id_launches"))    return (double) mi::add_id_launches();
     if (!strcmp(key, "mmv_id_blocks_launches")) return (double) mi::mmv_id_blocks_launches();
-    if (!strcmp(key, "mmq_id_blocks_launches")) return (double) mi::mmq_id_blocks_launches();
-    if (!strcmp(key, "mmq_id_blocks_ks"))   return (double) mi::mmq_id_blocks_last_ks();
+    if (!strcmp(key, "mmq_id_blocks_launches")) return (double) mi::mmq_id_stats(mi::MMQ_ID_BLOCKS).launches;
+    if (!strcmp(key, "mmq_id_blocks_ks"))   return (double) mi::mmq_id_stats(mi::MMQ_ID_BLOCKS).ks;
     if (!strncmp(key, "prof_", 5)) {
         std::string k(key + 5);
         const size_t us = k.rfind("_us"), nn = k.rfind("_n"), by = k.rfind("_bytes");

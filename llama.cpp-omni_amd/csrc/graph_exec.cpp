@@ -495,8 +495,8 @@ void compute_node(exec_state & s, int i) {
             return;
         case GGML_OP_MUL_MAT_ID: {                                       // expert mat-vecs, one (slot, token) pair per workgroup column (mmvk.hip k_mmv_id) -- or, K-quant experts
                                                                          // against a prefill ubatch, the pairs grouped by expert for the int8-MFMA kernel (mmq_id.hip);
-                                                                         // MXFP4 experts: mmv_mxfp4.hip / mmq_id_mxfp4.hip; the nine block forms: mmvq.hip
-                                                                         // k_mmv_blocks_id / (Q8_0, Q4_0, Q5_0, IQ4_NL) mmq_id_blocks.hip
+                                                                         // MXFP4 experts: mmv_mxfp4.hip / mmq_id.hip; the nine block forms: mmvq.hip
+                                                                         // k_mmv_blocks_id / (Q8_0, Q4_0, Q5_0, IQ4_NL) mmq_id.hip
             const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
             const mm_id_route r = route_mul_mat_id(n);
             if (!r.ok) { log_msg(GGML_LOG_LEVEL_ERROR, "[mi355x] graph_compute: MUL_MAT_ID %s reached the backend but has no kernel -- supports_op bug\n", n->name); abort(); }
@@ -510,11 +510,9 @@ void compute_node(exec_state & s, int i) {
             a.dst = (float *) n->data; a.dst_nb1 = n->nb[1]; a.dst_nb2 = n->nb[2]; a.K = as->ne[0]; a.nrows = as->ne[1];
             switch (r.path) {
                 case MM_ID_MMQ: {                                         // (bytes: every expert's matrix once -- the floor of a launch that touches them all)
-                    const bool mx = as->type == GGML_TYPE_MXFP4, bl = mmq_id_blocks_takes(as->type);
-                    prof_scope ps(s, mx ? "mmq_id_mxfp4" : bl ? "mmq_id_blocks" : "mmq_id", (double) std::min(as->ne[2], ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
-                    if (mx)      mmq_id_mxfp4({ a, s.c->moe_scratch, s.c->moe_scratch_bytes }, s.st);
-                    else if (bl) mmq_id_blocks({ a, s.c->moe_scratch, s.c->moe_scratch_bytes }, s.st);
-                    else         mmq_id_kquant({ a, s.c->moe_scratch, s.c->moe_scratch_bytes }, s.st);
+                    static const char * const scope[MMQ_ID_FAMILIES] = { "mmq_id", "mmq_id_mxfp4", "mmq_id_blocks" };
+                    prof_scope ps(s, scope[mmq_id_family(as->type)], (double) std::min(as->ne[2], ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
+                    mmq_id({ a, s.c->moe_scratch, s.c->moe_scratch_bytes }, s.st);
                     s.n_kernels += 2;                                     // the grouping launch and the matrix launch
                     break;
                 }

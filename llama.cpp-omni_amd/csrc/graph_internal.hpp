@@ -213,12 +213,12 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n);
 // the token count from which K-quant experts take the grouped kernel.  Above 33: up to there one mmv_id launch per node is what the per-pair tests count.
 static const int64_t MMQ_ID_MIN_TOKENS = 64;
 static_assert(MMQ_ID_MIN_TOKENS > 33, "the per-pair mat-vec keeps every token count up to 33");
-// ... and MXFP4 experts theirs (mmq_id_mxfp4.hip).  Above 64: the per-pair MXFP4 tests count one mmv_id_mxfp4 launch per node up to 64 tokens.  MI355X_MMQ_ID_MXFP4_MIN_TOKENS
+// ... and MXFP4 experts theirs (mmq_id.hip, mxfp4_dec).  Above 64: the per-pair MXFP4 tests count one mmv_id_mxfp4 launch per node up to 64 tokens.  MI355X_MMQ_ID_MXFP4_MIN_TOKENS
 // (read once, floor 65) moves it for measurements: mmq_id_mxfp4_min_tokens()
 static const int64_t MMQ_ID_MXFP4_MIN_TOKENS = 128;
 static_assert(MMQ_ID_MXFP4_MIN_TOKENS > 64, "the per-pair MXFP4 mat-vec keeps every token count up to 64");
 int64_t mmq_id_mxfp4_min_tokens();
-// ... and Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts theirs (mmq_id_blocks.hip).  Above 64: the per-pair tests keep their path.  65 is the measured value: at the Qwen3-30B-A3B
+// ... and Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts theirs (mmq_id.hip, the four f16-header Decs).  Above 64: the per-pair tests keep their path.  65 is the measured value: at the Qwen3-30B-A3B
 // and DeepSeek-V2-Lite expert shapes the grouped kernel is level with the per-pair one (Q4_0, 1.00 x) or ahead (up to 2.6 x) at 65 tokens already and ahead from there
 // on, for all four forms (profiles/moe_blocks_crossover.txt).  MI355X_MMQ_ID_BLOCKS_MIN_TOKENS (read once, floor 65) moves it for measurements: mmq_id_blocks_min_tokens()
 static const int64_t MMQ_ID_BLOCKS_MIN_TOKENS = 65;

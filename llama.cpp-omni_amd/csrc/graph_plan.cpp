@@ -349,14 +349,14 @@ mm_route route_mul_mat(const ggml_tensor * n) {
 //              expert alignment condition);
 //   MM_ID_MMQ  K-quant experts from MMQ_ID_MIN_TOKENS tokens on: the pairs grouped by expert on the device, mmq.hip's int8-MFMA body per (expert, 32 rows, <= 32 columns)
 //              (mmq_id.hip) -- a weight block is read once per 32 columns of its expert instead of once per pair.  MXFP4 experts from mmq_id_mxfp4_min_tokens() tokens
-//              on: the same grouping, one int8 MFMA per 17-byte block (mmq_id_mxfp4.hip), no alignment condition.  Same images, same admission: the path changes
+//              on: the same grouping and kernel frame, one int8 MFMA per 17-byte block, no alignment condition.  Same images, same admission: the path changes
 //              nothing in what supports_op takes.
 // Experts of the nine block forms of mmvq.hip (Q8_0, Q4_0/1, Q5_0/1, IQ4_NL/XS, Q2_K, Q3_K):
 //   MM_ID_MMV  the dense frame at one column behind the id indirection (mmvq.hip k_mmv_blocks_id), on the image the form's dense mat-vec reads (Q8_0 / Q8_1 / Q8_K);
 //              row and expert strides under the form's alignment, as supports_op states for MUL_MAT (4 bytes and a 4-byte-aligned base for Q4_1 / Q5_1 / Q2_K, 2 bytes
 //              for the rest);
 //   MM_ID_MMQ  Q8_0 / Q4_0 / Q5_0 / IQ4_NL (a 32-weight block against the Q8_0 image, no min term) from mmq_id_blocks_min_tokens() tokens on: the grouping, then one int8
-//              MFMA per block (mmq_id_blocks.hip).  Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_XS experts stay per-pair at every token count.
+//              MFMA per block (mmq_id.hip, the MXFP4 body with another block decoder).  Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_XS experts stay per-pair at every token count.
 // F16 / F32 / BF16 experts have no kernel with the id indirection: refused, they stay on the CPU.
 static int g_mmq_id = -1;                                     // option "mmq_id": -1 = MI355X_MMQ_ID decides (default on), 0 off (the cross-check switch), 1 on
 void mmq_id_set_mode(int m) { g_mmq_id = m; }
@@ -367,6 +367,17 @@ int64_t mmq_id_mxfp4_min_tokens() {
 int64_t mmq_id_blocks_min_tokens() {
     static const int64_t v = [] { const char * e = getenv("MI355X_MMQ_ID_BLOCKS_MIN_TOKENS"); const int64_t n = e ? atoll(e) : MMQ_ID_BLOCKS_MIN_TOKENS; return n < 65 ? (int64_t) 65 : n; }();
     return v;
+}
+// an admitted node takes the grouped path: the option, enough tokens for the type's family, a pair list and an expert histogram of bounded size, the kernel's LDS (the
+// columns' block scales: K up to ~70 k for K-quants, ~9 k for the 32-weight blocks) and, for K-quants, the MFMA body's vector-load alignment for expert 0 and (through
+// nb[2]) every other expert
+static bool mm_id_grouped(const ggml_tensor * as, const ggml_tensor * ids) {
+    static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
+    const int fam = mmq_id_family(as->type);
+    if (fam < 0 || !(g_mmq_id >= 0 ? g_mmq_id : env)) return false;
+    const int64_t K = as->ne[0], min_tokens = fam == MMQ_ID_KQUANT ? MMQ_ID_MIN_TOKENS : fam == MMQ_ID_MXFP4 ? mmq_id_mxfp4_min_tokens() : mmq_id_blocks_min_tokens();
+    if (ids->ne[1] < min_tokens || ids->ne[0] * ids->ne[1] > MMQ_ID_MAX_PAIRS || as->ne[2] > MMQ_ID_MAX_EXPERTS || mmq_id_lds_bytes(as->type, K) > MMQ_ID_LDS_MAX) return false;
+    return fam != MMQ_ID_KQUANT || (mmq_ok(as->type, K, as->data, as->nb[1]) && (as->ne[2] == 1 || mmq_ok(as->type, K, (const char *) as->data + as->nb[2], as->nb[1])));
 }
 mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     mm_id_route r = { false, ACT_NONE, MM_ID_MMV };
@@ -387,11 +398,7 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
         if (K < 32 || K % 32 != 0 || K > INT32_MAX || q80_image_bytes(K) > (size_t) 152 * 1024) return r;                 // one column's Q8_0 image in LDS
         if (as->nb[1] < row_size(t, K)) return r;
         r.ok = true; r.act = ACT_Q80;
-        // the grouped kernel: enough tokens, a pair list and an expert histogram of bounded size, its LDS (the columns' block scales: K up to ~9 k)
-        static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
-        if ((g_mmq_id >= 0 ? g_mmq_id : env) && ids->ne[1] >= mmq_id_mxfp4_min_tokens() && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS && as->ne[2] <= MMQ_ID_MAX_EXPERTS &&
-            mmq_id_mxfp4_lds_bytes(K) <= MMQ_ID_LDS_MAX)
-            r.path = MM_ID_MMQ;
+        if (mm_id_grouped(as, ids)) r.path = MM_ID_MMQ;
         return r;
     }
     if (blocks) {
@@ -402,10 +409,7 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
         const size_t al = (t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K) ? 4 : 2;                     // the forms' loads, for every expert's rows
         if (as->nb[1] % al != 0 || as->nb[2] % al != 0 || ((uintptr_t) as->data & (al - 1)) != 0) return r;
         r.ok = true; r.act = act;
-        static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
-        if ((g_mmq_id >= 0 ? g_mmq_id : env) && mmq_id_blocks_takes(t) && ids->ne[1] >= mmq_id_blocks_min_tokens() && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS &&
-            as->ne[2] <= MMQ_ID_MAX_EXPERTS && mmq_id_blocks_lds_bytes(K) <= MMQ_ID_LDS_MAX)
-            r.path = MM_ID_MMQ;
+        if (mm_id_grouped(as, ids)) r.path = MM_ID_MMQ;                                                                    // (Q8_0 / Q4_0 / Q5_0 / IQ4_NL only: mmq_id_family)
         return r;
     }
     if (K % 256 != 0 || K > INT32_MAX || q8k_image_bytes(K) > (size_t) 152 * 1024) return r;                              // one column's image in LDS
@@ -413,12 +417,7 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     const size_t al = t == GGML_TYPE_Q6_K ? 2 : 16;                                                                       // the vector loads' row alignment, as MUL_MAT -- for every expert's rows
     if (as->nb[1] % al != 0 || as->nb[2] % al != 0) return r;
     r.ok = true; r.act = ACT_Q8K;
-    // the grouped kernel: enough tokens, a pair list and an expert histogram of bounded size, the MFMA body's vector-load alignment for expert 0 and (through nb[2]) every
-    // other expert, and its LDS (the columns' block scales: K up to ~70 k)
-    static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
-    if ((g_mmq_id >= 0 ? g_mmq_id : env) && ids->ne[1] >= MMQ_ID_MIN_TOKENS && ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS && as->ne[2] <= MMQ_ID_MAX_EXPERTS &&
-        mmq_ok(t, K, as->data, as->nb[1]) && (as->ne[2] == 1 || mmq_ok(t, K, (const char *) as->data + as->nb[2], as->nb[1])) && mmq_id_lds_bytes(K) <= MMQ_ID_LDS_MAX)
-        r.path = MM_ID_MMQ;
+    if (mm_id_grouped(as, ids)) r.path = MM_ID_MMQ;
     return r;
 }
 bool mm_uses_mmq(const ggml_tensor * n)       { return route_mul_mat(n).path == MM_MMQ; }
@@ -450,7 +449,7 @@ size_t graph_act_scratch_need(const ggml_cgraph * g) {
     }
     return need;
 }
-// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip; K-quant and MXFP4 nodes alike): one grouping per node, the largest node's
+// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip; every family alike): one grouping per node, the largest node's
 size_t graph_moe_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;
     for (int i = 0; i < g->n_nodes; ++i) {

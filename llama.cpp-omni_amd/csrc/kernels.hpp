@@ -135,36 +135,30 @@ struct mmq_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_
 struct mmq_args { mmq_mat m[3]; int nmat; const void * act; size_t act_cs; int64_t K; int ncols; };
 bool mmq_ok(int type, int64_t K, const void * W, size_t w_rs);
 void mmq_kquant(const mmq_args & a, hipStream_t st);
-// ---- MUL_MAT_ID on K-quant experts against many tokens (mmq_id.hip): the pairs grouped by expert on the device (k_moe_group: pair list, tile table and tile count into
-// `scratch`, moe_group_bytes), then mmq.hip's body once per (expert, 32-row tile, <= 32-column slice), columns read and results stored through the pair list (k_mmq_id).
-// `m` as for mmv_id_kquant, its experts under mmq_ok's alignment (base, row stride, expert stride).  Nothing reads the ids on the host.
+// ---- MUL_MAT_ID against many tokens on the int8 matrix cores (mmq_id.hip): the pairs grouped by expert on the device (k_moe_group: pair list, tile table and tile count
+// into `scratch`, moe_group_bytes), then one workgroup per (expert, 32-row tile, <= 32-column slice), columns read and results stored through the pair list (k_mmq_id).
+// Nothing reads the ids on the host.  Three families of expert types, `m` as for the family's per-pair mat-vec:
+//   MMQ_ID_KQUANT  Q4_K / Q5_K / Q6_K: mmq.hip's body against the Q8_K images; the experts under mmq_ok's alignment (base, row stride, expert stride)
+//   MMQ_ID_MXFP4   gpt-oss prefill: one int8 MFMA per 32-weight block against the Q8_0 images -- ggml_vec_dot_mxfp4_q8_0's integers and product order, as
+//                  mmv_id_mxfp4; 17-byte blocks, no alignment condition
+//   MMQ_ID_BLOCKS  Q8_0 / Q4_0 / Q5_0 / IQ4_NL: a 32-weight block with an f16 scale and no min term against the Q8_0 images, one int8 MFMA per block -- the integers
+//                  of ggml_vec_dot_q8_0_q8_0 / _q4_0_q8_0 / _q5_0_q8_0 / _iq4_nl_q8_0; 2-byte aligned rows and experts, as mmv_id_blocks
 static const int64_t MMQ_ID_MAX_PAIRS = 1 << 20, MMQ_ID_MAX_EXPERTS = 4096;
 static const size_t  MMQ_ID_LDS_MAX = 64 * 1024;       // column scales of every K block + fold area + the slice's dst offsets (mmq_id_lds_bytes): no launch attribute needed
+enum { MMQ_ID_KQUANT, MMQ_ID_MXFP4, MMQ_ID_BLOCKS, MMQ_ID_FAMILIES };
 struct mmq_id_args { mmv_id_args m; void * scratch; size_t scratch_bytes; };
+struct mmq_id_stat { long launches; int ks; };          // nodes so far (the grouping and the matrix launch count as one), KS (waves splitting K) of the most recent launch (0: none yet)
+int    mmq_id_family(int type);                         // the family of an expert type, -1: the type has no grouped kernel
 size_t moe_group_bytes(int64_t n_pairs, int64_t n_expert);
-size_t mmq_id_lds_bytes(int64_t K);
-void mmq_id_kquant(const mmq_id_args & a, hipStream_t st);
-long mmq_id_launches();                                 // K-quant nodes so far (the grouping and the matrix launch count as one; stat "mmq_id_launches")
-int  mmq_id_last_ks();                                  // KS (waves splitting K) of the most recent mmq_id_kquant launch, 0 before the first (stat "mmq_id_ks"): read-only
-// the grouping on its own, for the matrix kernels of both files: one launch of k_moe_group into `scratch` (moe_group_bytes(n_ids * n_tokens, n_expert) bytes; the caller
-// checks the counts against MMQ_ID_MAX_*), the device pointers of what it writes.  Every id is clamped into [0, n_expert) there: the tile table names valid experts only.
+size_t mmq_id_lds_bytes(int type, int64_t K);           // (a type of a family) the slice's dst offsets + the columns' block scales + the widest fold: <= MMQ_ID_LDS_MAX is the route's condition
+void   mmq_id(const mmq_id_args & a, hipStream_t st);
+mmq_id_stat mmq_id_stats(int family);                   // read-only: the stats "mmq_id_launches" / "mmq_id_ks", "mmq_id_mxfp4_*", "mmq_id_blocks_*"
+// the grouping on its own: one launch of k_moe_group into `scratch` (moe_group_bytes(n_ids * n_tokens, n_expert) bytes; the caller checks the counts against
+// MMQ_ID_MAX_*), the device pointers of what it writes.  Every id is clamped into [0, n_expert) there: the tile table names valid experts only.
 struct moe_tile { int expert, first, ncols; };          // one non-empty (expert, <= 32-column slice): the expert, the slice's first position in the pair list, its column count
 struct moe_group_out { const int * count; const moe_tile * tiles; const int * list; };
 int64_t moe_tile_bound(int64_t n_pairs, int64_t n_expert);      // the host-side bound on the tile count: the matrix kernels' grid y
 moe_group_out moe_group_launch(const mmv_id_args & m, void * scratch, hipStream_t st);
-// ---- the same on MXFP4 experts (mmq_id_mxfp4.hip; gpt-oss prefill): k_moe_group's tables, then one int8 MFMA per 32-weight block and (32 rows, <= 32 columns) against
-// the Q8_0 images -- ggml_vec_dot_mxfp4_q8_0's integers and product order, as mmv_id_mxfp4.  `m` as for mmv_id_mxfp4: 17-byte blocks, no alignment condition.
-size_t mmq_id_mxfp4_lds_bytes(int64_t K);               // the slice's dst offsets + the columns' block scales + the widest fold: <= MMQ_ID_LDS_MAX is the route's condition
-void mmq_id_mxfp4(const mmq_id_args & a, hipStream_t st);
-long mmq_id_mxfp4_launches();                           // MXFP4 nodes so far (grouping + matrix launch = one; stat "mmq_id_mxfp4_launches")
-int  mmq_id_mxfp4_last_ks();                            // KS of the most recent mmq_id_mxfp4 launch, 0 before the first (stat "mmq_id_mxfp4_ks"): read-only
-// ---- the same on Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts (mmq_id_blocks.hip): a 32-weight block with an f16 scale and no min term against the Q8_0 images, one int8 MFMA
-// per block -- the integers of ggml_vec_dot_q8_0_q8_0 / _q4_0_q8_0 / _q5_0_q8_0 / _iq4_nl_q8_0.  `m` as for mmv_id_blocks: 2-byte aligned rows and experts.
-bool   mmq_id_blocks_takes(int type);                   // one of the four types
-size_t mmq_id_blocks_lds_bytes(int64_t K);              // as mmq_id_mxfp4_lds_bytes
-void mmq_id_blocks(const mmq_id_args & a, hipStream_t st);
-long mmq_id_blocks_launches();                          // nodes so far (grouping + matrix launch = one; stat "mmq_id_blocks_launches")
-int  mmq_id_blocks_last_ks();                           // KS of the most recent mmq_id_blocks launch, 0 before the first (stat "mmq_id_blocks_ks"): read-only
 // ---- Q4_K weights against a prefill ubatch (> 64 columns) on the int8 matrix cores, tiled (mmq_tile.hip): up to 3 matrices sharing the block-major
 // Q8_K image of the activations (quantize_q8k_tile_image); `resid`: dst = W.x + resid (single matrix, un-split); split-K slabs / deferred reductions as gemm_f16_multi
 struct mmqt_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_t M; const float * resid = nullptr; size_t resid_cs = 0; };

@@ -1,4 +1,4 @@
-// blocks_dev.hpp -- what the mat-vec Forms of the 32-weight block formats (mmvq.hip) and the expert-grouped int8-MFMA kernel on the same blocks (mmq_id_blocks.hip)
+// blocks_dev.hpp -- what the mat-vec Forms of the 32-weight block formats (mmvq.hip) and the expert-grouped int8-MFMA kernel on the same blocks (mmq_id.hip)
 // share: the fifth-bit spread of Q5_0 / Q5_1 and the IQ4_NL table look-up.
 #pragma once
 #include "../kernels.hpp"

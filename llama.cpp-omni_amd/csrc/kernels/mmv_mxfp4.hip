@@ -21,7 +21,7 @@ namespace mi {
 
 extern __shared__ __attribute__((aligned(16))) char mx_lds[];
 
-// (mxfp4_lut4, the table look-up of four nibbles, and e8m0_half, half the block scale: mxfp4_dev.hpp -- shared with the grouped kernel, mmq_id_mxfp4.hip)
+// (mxfp4_lut4, the table look-up of four nibbles, and e8m0_half, half the block scale: mxfp4_dev.hpp -- shared with the grouped kernel, mmq_id.hip)
 
 struct mx_id_dev {
     const char * as; size_t as_nb1, as_nb2; int n_expert;

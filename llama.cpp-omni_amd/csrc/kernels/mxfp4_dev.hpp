@@ -1,4 +1,4 @@
-// mxfp4_dev.hpp -- what the two MXFP4 kernels share (mmv_mxfp4.hip: the per-pair mat-vec, mmq_id_mxfp4.hip: the expert-grouped int8-MFMA kernel): the 16-entry
+// mxfp4_dev.hpp -- what the two MXFP4 kernels share (mmv_mxfp4.hip: the per-pair mat-vec, mmq_id.hip: the expert-grouped int8-MFMA kernel): the 16-entry
 // int8 table look-up of kvalues_mxfp4 (ggml-common.h:1094) and half the E8M0 block scale (ggml_e8m0_to_fp32_half, ggml-impl.h:471-489).
 #pragma once
 #include "../kernels.hpp"

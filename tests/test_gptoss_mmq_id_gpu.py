@@ -1,5 +1,5 @@
-"""MUL_MAT_ID of MXFP4 experts (gpt-oss) against a prefill ubatch (`-m gpu`): the expert-grouped int8-MFMA path (kernels/mmq_id_mxfp4.hip: k_moe_group sorts the pairs
-by expert on the device, k_mmq_id_mxfp4 runs one MFMA per 17-byte block and (expert, 32-row tile, <= 32-column slice)), through the backend C-ABI and against the
+"""MUL_MAT_ID of MXFP4 experts (gpt-oss) against a prefill ubatch (`-m gpu`): the expert-grouped int8-MFMA path (kernels/mmq_id.hip: k_moe_group sorts the pairs
+by expert on the device, k_mmq_id runs one MFMA per 17-byte block and (expert, 32-row tile, <= 32-column slice)), through the backend C-ABI and against the
 reference CPU backend on the same graph.
 
 Bars: NMSE <= 1e-9 against the reference over the whole output AND for every (token, slot) pair on its own -- the project's bar for the three id kernels against the
@@ -58,7 +58,7 @@ def _delta(be, s0):
 
 
 def _ks_rule(n_expert, n_used, T, M, K):
-    """the launcher's rule (mmq_id_mxfp4.hip), restated: row tiles = ceil(M / 32), bound = min(pairs, experts) + pairs / 32, steps of 8 blocks"""
+    """the launcher's rule (mmq_id.hip), restated: row tiles = ceil(M / 32), bound = min(pairs, experts) + pairs / 32, steps of 8 blocks"""
     pairs = n_used * T
     row_tiles, bound, nstep, ks = (M + 31) // 32, min(pairs, n_expert) + pairs // 32, (K // 32 + 7) // 8, 1
     while ks < 8 and row_tiles * bound * ks * 2 <= 3072 and ks * 4 <= nstep:

@@ -1,7 +1,7 @@
 """A gpt-oss MODEL whose prompt reaches the expert-grouped MXFP4 kernel (`-m gpu`): the synthetic `gpt-oss` GGUF of tools/make_synth_gptoss_gguf.py (2 layers, 8 MXFP4
 experts of n_ff 288 with 4 used; see tests/test_gptoss_model_gpu.py) decoded by oracle/_ref/llama-bench-min through the reference's libllama on the plug-in.  The prompt
 file holds the fixture's separated ids, cycled, and is decoded in batches of 160 tokens (`-b 160`), each ONE ubatch that reaches the expert nodes at 160 tokens --
-above MMQ_ID_MXFP4_MIN_TOKENS -- on kernels/mmq_id_mxfp4.hip; the 32 greedy steps behind it run at one token on the per-pair kernel.
+above MMQ_ID_MXFP4_MIN_TOKENS -- on kernels/mmq_id.hip; the 32 greedy steps behind it run at one token on the per-pair kernel.
 
 Why two batches of 160 and not one: only the last token of a batch asks for logits, and libllama cuts the LAST layer down to the rows that are output in front of its
 FFN.  So a batch of 160 tokens runs the experts of every layer but the last at 160 tokens and those of the last layer at ONE: 3 x (layers - 1) = 3 grouped nodes, measured

@@ -1,5 +1,5 @@
-"""MUL_MAT_ID of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts against a prefill ubatch (`-m gpu`): the expert-grouped int8-MFMA path (kernels/mmq_id_blocks.hip: k_moe_group
-sorts the pairs by expert on the device, k_mmq_id_blocks runs one MFMA per 32-weight block and (expert, 32-row tile, <= 32-column slice)), through the backend C-ABI
+"""MUL_MAT_ID of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts against a prefill ubatch (`-m gpu`): the expert-grouped int8-MFMA path (kernels/mmq_id.hip: k_moe_group
+sorts the pairs by expert on the device, k_mmq_id runs one MFMA per 32-weight block and (expert, 32-row tile, <= 32-column slice)), through the backend C-ABI
 and against the reference CPU backend on the same graph.
 
 Bars: NMSE <= 1e-8 against the reference over the whole output AND for every (token, slot) pair on its own -- the project's bar for these forms' integer mat-vecs
@@ -57,7 +57,7 @@ def _delta(be, s0):
 
 
 def _ks_rule(n_expert, n_used, T, M, K):
-    """the launcher's rule (mmq_id_blocks.hip), restated: row tiles = ceil(M / 32), bound = min(pairs, experts) + pairs / 32, steps of 8 blocks; the split doubles
+    """the launcher's rule (mmq_id.hip), restated: row tiles = ceil(M / 32), bound = min(pairs, experts) + pairs / 32, steps of 8 blocks; the split doubles
     while the grid bound stays inside 3072 / 2 waves and every wave keeps at least 4 steps"""
     pairs = n_used * T
     row_tiles, bound, nstep, ks = (M + 31) // 32, min(pairs, n_expert) + pairs // 32, (K // 32 + 7) // 8, 1
@@ -184,6 +184,8 @@ CASES = [
     ("iq4_nl", 8, 4, 161, 64, 288, 1, "one", 1),
     ("iq4_nl", 8, 2, 128, 70, 288, 1, "ragged", 1),
     ("iq4_nl", 8, 4, 128, 70, 2880, 4, "rand", 4),
+    ("q5_0", 8, 2, 128, 64, 1056, 1, "rand", 2),                      # 33 blocks, 5 steps over 2 waves; and 249 blocks, 32 steps over 8 waves (the widest fold): the
+    ("q8_0", 8, 2, 128, 70, 7968, 2, "ragged", 8),                    # splits the MXFP4 table reaches with the same shapes
 ]
 
 

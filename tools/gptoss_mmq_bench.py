@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/gptoss_mmq_bench.py -- the expert launches of one gpt-oss-20b layer at the PREFILL shape (32 MXFP4 experts, 4 used, K = M = 2880: a gate / up leg with b
 broadcast over the slots, a down leg with b per slot) at 65 / 128 / 512 / 2048 tokens, timed as replayed captures through the backend C-ABI on both MUL_MAT_ID paths in
-the same process: option mmq_id = 1 (the expert-grouped int8-MFMA kernel, mmq_id_mxfp4.hip: one grouping launch + one matrix launch per node) and mmq_id = 0 (the
+the same process: option mmq_id = 1 (the expert-grouped int8-MFMA kernel, mmq_id.hip: one grouping launch + one matrix launch per node) and mmq_id = 0 (the
 per-pair mat-vec, mmv_mxfp4.hip -- the yardstick: the kernel every token count ran on before the grouped path existed).
 
 The grouped path starts at MMQ_ID_MXFP4_MIN_TOKENS = 128 tokens by default; the tool sets MI355X_MMQ_ID_MXFP4_MIN_TOKENS=65 (unless the environment has a value) before

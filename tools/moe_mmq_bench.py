@@ -13,7 +13,7 @@ rounds show the run-to-run spread.  Per leg and token count:
     TOP/s  = 2 * pairs * M * K int8 operations per node / the grouped path's time.
 MI355X_MMQ_ID_NT4=1 in the environment keeps every tile of the grouped kernel on the four-column-group body (the measurement behind the per-tile branch).
 
---legs blocks: the same for Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts (mmq_id_blocks.hip against mmvq.hip k_mmv_blocks_id), at the Qwen3-30B-A3B gate / up shape and at the
+--legs blocks: the same for Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts (mmq_id.hip against mmvq.hip k_mmv_blocks_id), at the Qwen3-30B-A3B gate / up shape and at the
 DeepSeek-V2-Lite down shape (64 experts, 6 used, K 1408, M 2048); --types picks among the four.  MI355X_MMQ_ID_BLOCKS_MIN_TOKENS=65 in the environment puts every token
 count from 65 on the grouped path (the crossover measurement behind MMQ_ID_BLOCKS_MIN_TOKENS, profiles/moe_blocks_crossover.txt).
 
