@@ -832,7 +832,7 @@ void exec_fattn(exec_state & s, int i) {
     fattn_args f; tdesc m;
     fill_fattn_args(n, f, m);
     if ((n->src[0]->ne[0] != 64 && n->src[0]->ne[0] != 128) || n->src[2]->ne[0] != n->src[0]->ne[0] || n->src[1]->type != GGML_TYPE_F16) {      // other head sizes / cache types: the generic kernel, no fused stage
-        if (fattn_wide_takes(f) && fattn_scratch_bytes(f) > 0) {      // head sizes 256 / 576 over a deep cache: workspace of the KV slices (+ the merge launch)
+        if (fattn_wide_takes(f) && fattn_scratch_bytes(f) > 0) {      // a head size of fattn_wide.hip over a deep cache: workspace of the KV slices, columns x slices x (DV + 2) floats (+ the merge launch)
             f.scratch = fa_scratch_take(s, FA_KV_SPLIT, n); f.scratch_bytes = s.c->fa_scratch_bytes;
             ++s.n_kernels;
         }

@@ -210,7 +210,7 @@ bool supports_op(const ggml_tensor * op) {
             if (q->type != GGML_TYPE_F32 || k->type != v->type || op->type != GGML_TYPE_F32) return false;
             if (k->type != GGML_TYPE_F16 && k->type != GGML_TYPE_F32 && k->type != GGML_TYPE_BF16 && k->type != GGML_TYPE_Q8_0 && k->type != GGML_TYPE_Q4_0) return false;
             if (q->ne[0] != k->ne[0]) return false;
-            // the MFMA / streaming / one-token kernels (F16 cache, head 64 / 128); anything else -- other head sizes, a quantised / BF16 / F32 cache -- fattn_any.hip
+            // the MFMA / streaming / one-token kernels (F16 cache, head 64 / 128); anything else -- other head sizes, a quantised / BF16 / F32 cache -- fattn_wide.hip where fa_wide_plan takes it, else fattn_any.hip
             const bool special = k->type == GGML_TYPE_F16 && (q->ne[0] == 64 || q->ne[0] == 128) && v->ne[0] == q->ne[0];
             if (!special && (q->ne[0] > 576 || v->ne[0] > 576)) return false;
             if ((k->type == GGML_TYPE_Q8_0 || k->type == GGML_TYPE_Q4_0) && (k->ne[0] % 32 != 0 || v->ne[0] % 32 != 0)) return false;

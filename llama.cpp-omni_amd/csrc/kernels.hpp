@@ -361,7 +361,7 @@ bool   fattn_pre_ok(const fattn_args & a);
 void   fattn_set_dma(int m);      // the LDS-DMA ring form of the prefill kernel (head 128, >= 512 workgroups): -1 default (on), 0 off, 1 on
 long   fattn_dma_launches();
 void   fattn_set_gqa(bool on);   // matrix-core decode kernel on (default) / off: the streaming kernel takes every few-token shape (cross-check)
-void   fattn_set_wide(int m);     // option "fattn_wide": the matrix-core kernel for head sizes 256 / 256 and 576 / 512 (fattn_wide.hip): -1 default (on), 0 off (the generic kernel), 1 on
+void   fattn_set_wide(int m);     // option "fattn_wide": the matrix-core kernel for head sizes 40 / 72 / 80 / 96 / 112 / 256, 192 / 128 and 576 / 512 (fattn_wide.hip): -1 default (on), 0 off (the generic kernel), 1 on
 long   fattn_wide_launches();
 bool   fattn_wide_takes(const fattn_args & a);    // that kernel will run (fa_wide_plan); fattn_scratch_bytes() is then its slices' workspace, 0 with one slice
 bool   fattn_uses_mma(const fattn_args & a);      // the matrix-core (prefill) kernel will run: out16 is honoured

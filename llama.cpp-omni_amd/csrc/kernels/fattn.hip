@@ -427,7 +427,8 @@ static gqa_plan fa_gqa_plan(const fattn_args & f) {
     return p;
 }
 
-// Head sizes 256 / 256 (Gemma 2 / 3) and 576 / 512 (DeepSeek MLA) over an F16 cache: k_fattn_wide (fattn_wide.hip).  The single place that decides
+// Head sizes 40, 72, 80, 96, 112 (K and V alike), 192 / 128 (DeepSeek V2 before the absorption), 256 / 256 (Gemma 2 / 3) and 576 / 512 (DeepSeek MLA) over
+// an F16 cache -- the pairs of fattn_wide_dims, and no others: (256, 128), 48 ... stay generic --: k_fattn_wide (fattn_wide.hip).  The single place that decides
 // whether that kernel takes a node, in how many KV slices and with how many waves: consulted by the dispatch below, by fattn_scratch_bytes and through
 // fattn_wide_takes by the executor.  Everything it refuses stays on the generic kernel (fattn_any.hip).
 // Slices: up to FA_WIDE_DIRECT_TILES = 16 tiles of 32 rows (n_kv <= 512) one workgroup per column-tile group walks the whole range and finishes its rows: one
@@ -584,7 +585,7 @@ void flash_attn_ext_f16(const fattn_args & f, hipStream_t st) {
         a.pre = { (const char *) p.qraw, p.q_hs, (const char *) p.kraw, p.k_hs, (const char *) p.vraw, p.v_hs, p.qw, p.kw, p.pos, p.ff, p.eps, make_rope_dev(p.rp),
                   (char *) p.kcache, p.kc_rs, (char *) p.vcache, p.vc_rs, (const char *) p.kidx, (const char *) p.vidx, p.idx_is64 };
     }
-    if (const wide_plan wp = fa_wide_plan(f); wp.ok) {                // head sizes 256 / 256 and 576 / 512, F16 cache: the matrix-core kernel of fattn_wide.hip
+    if (const wide_plan wp = fa_wide_plan(f); wp.ok) {                // the head sizes of fattn_wide_dims, F16 cache: the matrix-core kernel of fattn_wide.hip
         const int DV = (int) f.v.ne[0];
         a.nsplit = 1; a.part = nullptr; a.tile_map = nullptr; a.map_nqb = 0;
         if (wp.nsplit > 1 && f.scratch && f.scratch_bytes >= fattn_scratch_bytes(f)) { a.nsplit = wp.nsplit; a.part = (float *) f.scratch; }   // (no workspace: one slice, still correct)
@@ -592,8 +593,12 @@ void flash_attn_ext_f16(const fattn_args & f, hipStream_t st) {
         if (a.nsplit > 1) {
             const int nblk = (int) ((a.nh * DV + 255) / 256);
             const dim3 grid((unsigned) (a.nq * a.ns * nblk));
-            if (DV == 256) k_fattn_merge<256><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
-            else           k_fattn_merge<512><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
+#define FA_MERGE(DD) case DD: k_fattn_merge<DD><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0); break
+            switch (DV) {                                             // (k_fattn_merge indexes quads of a row: DV % 4 == 0)
+                FA_MERGE(40); FA_MERGE(72); FA_MERGE(80); FA_MERGE(96); FA_MERGE(112); FA_MERGE(128); FA_MERGE(256); FA_MERGE(512);
+                default: fprintf(stderr, "[mi355x] flash_attn: no merge kernel for head size %d\n", DV); abort();
+            }
+#undef FA_MERGE
         }
         return;
     }

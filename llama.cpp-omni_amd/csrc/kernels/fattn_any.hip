@@ -1,5 +1,6 @@
-// fattn_any.hip -- FLASH_ATTN_EXT for what the specialised kernels do not take: other head sizes (D not in {64, 128}, or K and V heads of
-// different size: 40 / 48 / 72 / 80 / 96 / 192 / 256, 576 x 512) and other cache types (F32, BF16, Q8_0, Q4_0 K / V -- a quantised KV cache):
+// fattn_any.hip -- FLASH_ATTN_EXT for what the specialised kernels do not take: head sizes that are neither 64 / 128 nor on fattn_wide_dims (48, 256 / 128,
+// ...), the head sizes of fattn_wide_dims (40 / 72 / 80 / 96 / 112, 192 / 128, 256, 576 / 512) where fa_wide_plan refuses the node (ALiBi, a mask per head,
+// unaligned rows, option "fattn_wide" = 0) and other cache types at any head size (F32, BF16, Q8_0, Q4_0 K / V -- a quantised KV cache):
 // one WAVE per (query row, head, sequence), lanes over the head dimension.
 // Not a fast kernel -- it exists so that such a node stays on the device instead of being handed to the CPU backend by supports_op (a
 // scheduler split + two transfers per layer); the Qwen3 / TTS / Whisper shapes never come here.

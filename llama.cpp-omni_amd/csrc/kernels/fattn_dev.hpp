@@ -48,7 +48,7 @@ void flash_attn_gs(const fa_dev & a, int D, const float * rope_tab, float * part
 // any other head size (fattn_any.hip): one wave per (query row, head, sequence)
 bool fattn_any_ok(int64_t Dk, int64_t Dv);
 void flash_attn_ext_any(const fa_dev & a, int Dk, int Dv, int kv_type, hipStream_t st);      // kv_type: F16 / F32 / BF16 / Q8_0 / Q4_0 (K and V alike)
-// head sizes 256 / 256 and 576 / 512 over an F16 cache on the matrix cores (fattn_wide.hip): 32-column tiles of (token, head) pairs as k_fattn_gqa, K / V tiles shared
+// head sizes 40, 72, 80, 96, 112, 256 (K and V alike), 192 / 128 and 576 / 512 over an F16 cache on the matrix cores (fattn_wide.hip; fattn_wide_dims is the list): 32-column tiles of (token, head) pairs as k_fattn_gqa, K / V tiles shared
 // through LDS by the waves of a workgroup, KV range in a.nsplit slices (-> a.part [column][slice][DV + 2] when > 1); fa_wide_plan (fattn.hip) decides
 bool fattn_wide_dims(int64_t Dk, int64_t Dv);
 int  fattn_wide_max_tiles();                      // 32-row KV tiles a slice may hold (the kernel's live-tile bitmap)

@@ -1,5 +1,7 @@
-// fattn_wide.hip -- FLASH_ATTN_EXT on the matrix cores for the wide heads: (DK, DV) = (256, 256) (Gemma 2 / 3) and (576, 512) (DeepSeek MLA after
-// the absorption: one KV head, K rows 576 wide, V rows 512 wide), F16 K / V, f32 Q, one kernel for decode and prefill.
+// fattn_wide.hip -- FLASH_ATTN_EXT on the matrix cores for the head sizes beside 64 / 128: (DK, DV) = (256, 256) (Gemma 2 / 3), (576, 512) (DeepSeek MLA
+// after the absorption: one KV head, K rows 576 wide, V rows 512 wide), and the sizes that are no multiple of the MFMA extents: (40, 40), (72, 72) (SigLip-class
+// towers), (80, 80) (Phi-2, StableLM-3B), (96, 96) (Phi-3-mini), (112, 112) and (192, 128) (DeepSeek V2 / V3 before the absorption).  F16 K / V, f32 Q, one
+// kernel for decode and prefill.
 //
 // Arithmetic is fattn_mma.hip's (which restates ops.cpp:7912-8148): Q rounded to f16, s = K.q * scale [-> softcap * tanh] + mask, online
 // soft-max in f32 with base-2 exponentials, P rounded to f16 for the second product, O in f32, sinks folded at the end, then 1 / S.
@@ -19,6 +21,22 @@
 //     fragment (72 registers' worth) lives in lane-private LDS slots: with it in registers the compiler still spilled 140 - 160 bytes.
 //     LDS: K 37376 + V^T 34816 + exchange 16384 + Q 73728 + 512 (bitmap) = 162816 of 163840 bytes: one workgroup per CU.
 //     MLA decode (128 heads = 4 column tiles) reads a cache row twice per token -- once per workgroup -- not 128 times.
+//   40 ... 112 and 192 / 128: as 256 / 256 (NDH = 1, four column tiles per workgroup) on PADDED extents: DKP = DK rounded up to 16 (40 -> 48, 72 -> 80), DVP = DV
+//     rounded up to 32 (40 -> 64, 72 / 80 -> 96, 112 -> 128).  The K tile's columns DK .. DKP - 1 (they enter every score) and the V^T tile's rows DV .. DVP - 1
+//     are zeros the kernel writes once, before the bitmap barriers: the staging stores never reach them.  DK % 8 == 0, so the 8 elements a lane holds of the
+//     Q fragment's last step are inside the row or past it as a whole: past it they are zeros and no address is formed there.  The staging loops' last round
+//     is guarded where 256 threads do not divide the chunks (DK = 80: 320 K chunks; DV = 80: 160 V chunk pairs); where they do, the guard is a constant and
+//     the 256 and 576 instances keep their loops.  Only d < DV is stored (DV % 4 == 0: a quad is inside the row or in the padding), to dst and to a.part.
+//     LDS: K 3 584 (40) ... 12 800 (192) + V^T 4 352 (40) ... 8 704 (112, 128) + 512 bytes (bitmap): no attribute, several workgroups per CU.
+// LDS banks (ds_read_b128: bank = dword address mod 64, four 16-lane groups, within a group lq takes 16 values distinct mod 16).  K fragment: lane (lq, hb) reads 16
+//   bytes at row lq: 16-byte slot (lq * KLD / 8 + const) mod 16, so the read is conflict-free iff KLD / 8 is odd.  DKP is a multiple of 16, KLD = DKP + 8 makes
+//   KLD / 8 odd at every size (7, 11, 11, 13, 15, 25; 33 and 73 as before); DK + 8 would be even at 40 and 72 (2-way).  V^T fragment: b32 reads (banks mod 32, the two
+//   32-lane halves apart) of words (row lq) * 17 + const: 17 is odd, 32 rows on 32 banks, conflict-free whatever DV.  The transposing V^T writes are not: thread c
+//   writes row 8 * (c % (DV / 8)) + .., word c / (DV / 8), bank (8 * o + p) mod 32 -- 8-way at DV = 256 (32 chunks per row, p constant over 32 lanes), 2- to 4-way at
+//   the small sizes where a 32-lane half spans several p.  Derived from the bank rule, not counted: no counter run was made.
+// Registers (-Rpass-analysis=kernel-resource-usage, gfx950, VGPR / AGPR, plain and soft-cap instance; scratch 0 in every instance, no spill to memory):
+//   40: 128 / 48, 130 / 48    72: 174 / 64, 176 / 64    80: 174 / 64, 176 / 64    96: 178 / 64, 180 / 64    112: 198 / 80, 200 / 80    192 / 128: 214 / 80, 216 / 80
+//   256: 256 / 194, 256 / 196    576 / 512: 256 / 221, 256 / 226 (as before the small sizes were added; two waves per SIMD at 40 ... 96, one above)
 // Per live KV tile, two barriers (three with the exchange) and single-buffered LDS; the global loads are register-staged and overlap the
 // matrix work of the other operand: V(t) is in flight under K(t).Q, K(t + 1) under P.V(t).
 //
@@ -46,13 +64,15 @@ constexpr int   FW_MAXT = 4096;                  // live-tile bitmap capacity: n
 constexpr float FW_LOG2E = 1.4426950408889634f;
 
 template <int DK, int DV> struct fw_cfg {
-    static constexpr int KLD  = DK + 8;          // K tile row pitch in halfs (16-byte aligned rows, conflict-free b128 reads)
+    static constexpr int DKP  = (DK + 15) / 16 * 16;   // DK rounded up to whole MFMA steps: the K tile's columns DK .. DKP - 1 are zeros
+    static constexpr int DVP  = (DV + 31) / 32 * 32;   // DV rounded up to whole 32-dim blocks of O^T: the V^T tile's rows DV .. DVP - 1 are zeros
+    static constexpr int KLD  = DKP + 8;         // K tile row pitch in halfs (16-byte aligned rows; KLD / 8 is odd: conflict-free b128 reads)
     static constexpr int VLDW = 17;              // V^T row pitch in 32-bit words (odd: spreads the transposing writes)
     static constexpr int KB   = FW_KT * KLD * 2; // bytes of the K tile
-    static constexpr int VB   = DV * VLDW * 4;   // bytes of the V^T tile
+    static constexpr int VB   = DVP * VLDW * 4;  // bytes of the V^T tile
     static constexpr int NDH  = DV > 256 ? 2 : 1;                  // waves that share a column tile (halves of DK for the scores, of DV for O^T)
     static constexpr int XB   = NDH > 1 ? FW_NW * 16 * 64 * 4 : 0; // bytes of the partial-score exchange
-    static constexpr int QB   = NDH > 1 ? FW_NW * (DK / 16 / NDH) * 64 * 16 : 0;   // bytes of the waves' Q fragments kept in LDS (576: the registers go to O^T and the staging)
+    static constexpr int QB   = NDH > 1 ? FW_NW * (DKP / 16 / NDH) * 64 * 16 : 0;   // bytes of the waves' Q fragments kept in LDS (576: the registers go to O^T and the staging)
 };
 
 extern __shared__ __attribute__((aligned(16))) char fw_lds[];
@@ -61,11 +81,14 @@ template <int DK, int DV, bool CAP>
 __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const int nct) {
     constexpr int KLD = fw_cfg<DK, DV>::KLD, VLDW = fw_cfg<DK, DV>::VLDW;
     constexpr int NDH = fw_cfg<DK, DV>::NDH, CTW = FW_NW / NDH;   // column tiles per workgroup
-    constexpr int NKS = DK / 16 / NDH, NDB = DV / 32 / NDH;       // this wave's MFMA steps over DK, its 32-dim blocks of O^T
+    constexpr int DKP = fw_cfg<DK, DV>::DKP, DVP = fw_cfg<DK, DV>::DVP;
+    constexpr int NKS = DKP / 16 / NDH, NDB = DVP / 32 / NDH;     // this wave's MFMA steps over DK, its 32-dim blocks of O^T
     constexpr int NT  = 64 * FW_NW;
-    constexpr int KCH = FW_KT * (DK / 8) / NT;            // 16-byte K chunks per thread and tile
-    constexpr int VCH = (FW_KT / 2) * (DV / 8) / NT;      // 16-byte chunk PAIRS (rows 2p, 2p + 1) of V per thread and tile
-    static_assert(FW_KT * (DK / 8) % NT == 0 && (FW_KT / 2) * (DV / 8) % NT == 0, "whole chunks per thread");
+    constexpr int KTOT = FW_KT * (DK / 8), VTOT = (FW_KT / 2) * (DV / 8);   // 16-byte K chunks, 16-byte chunk PAIRS (rows 2p, 2p + 1) of V per tile
+    constexpr int KCH = (KTOT + NT - 1) / NT, VCH = (VTOT + NT - 1) / NT;   // ... per thread
+    constexpr bool KRAG = KTOT % NT != 0, VRAG = VTOT % NT != 0;            // the last round has idle threads (false: the guards below fold away)
+    static_assert(DK % 8 == 0 && DV % 8 == 0, "16-byte chunks of K and V rows");
+    static_assert(NDH == 1 || (DKP == DK && DVP == DV && DK % (16 * NDH) == 0 && DV % (32 * NDH) == 0), "the shared column tile splits whole steps");
     _Float16 * Ks = (_Float16 *) fw_lds;
     uint32_t * Vt = (uint32_t *) (fw_lds + fw_cfg<DK, DV>::KB);
     float    * Xs = (float *) (fw_lds + fw_cfg<DK, DV>::KB + fw_cfg<DK, DV>::VB);                 // [wave][16][64] partial scores (NDH == 2)
@@ -116,6 +139,15 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
         }
     };
 
+    // ---- the padding the matrix cores read: zeros written HERE, once (store_k / store_v never touch it; the barriers below publish it)
+    if constexpr (DKP != DK) {                            // K columns DK .. DKP - 1: one 16-byte chunk per row
+        static_assert(DKP - DK == 8, "DK % 8 == 0");
+        if (tid < FW_KT) *(u32x4 *) (Ks + tid * KLD + DK) = u32x4{ 0u, 0u, 0u, 0u };
+    }
+    if constexpr (DVP != DV) {                            // V^T rows DV .. DVP - 1, the 16 words the fragments read
+        for (int i = tid; i < (DVP - DV) * 16; i += NT) Vt[(DV + (i >> 4)) * VLDW + (i & 15)] = 0u;
+    }
+
     // ---- live-tile bitmap of this slice (bit t - t_lo)
     for (int i = tid; i < FW_MAXT / 32; i += NT) live[i] = a.mask ? 0u : 0xffffffffu;
     __syncthreads();
@@ -145,6 +177,7 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
 #pragma unroll
         for (int i = 0; i < KCH; ++i) {
             const int c = tid + i * NT, row = c / (DK / 8), o = c % (DK / 8);
+            if (KRAG && c >= KTOT) continue;
             const int kv = t * FW_KT + row;
             const bool ok = kv < a.nkv;
             kreg[i] = *(const u32x4 *) (kbase + (int64_t) (ok ? kv : a.nkv - 1) * a.knb1 + o * 16);
@@ -155,6 +188,7 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
 #pragma unroll
         for (int i = 0; i < KCH; ++i) {
             const int c = tid + i * NT, row = c / (DK / 8), o = c % (DK / 8);
+            if (KRAG && c >= KTOT) continue;
             *(u32x4 *) (Ks + row * KLD + o * 8) = kreg[i];
         }
     };
@@ -162,6 +196,7 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
 #pragma unroll
         for (int i = 0; i < VCH; ++i) {
             const int c = tid + i * NT, o = c % (DV / 8), p = c / (DV / 8);
+            if (VRAG && c >= VTOT) continue;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int kv = t * FW_KT + 2 * p + j;
@@ -175,6 +210,7 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
 #pragma unroll
         for (int i = 0; i < VCH; ++i) {
             const int c = tid + i * NT, o = c % (DV / 8), p = c / (DV / 8);
+            if (VRAG && c >= VTOT) continue;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 Vt[(8 * o + 2 * e)     * VLDW + p] = (vreg[i][0][e] & 0xffffu) | (vreg[i][1][e] << 16);
@@ -193,11 +229,14 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
         const char * qr = a.q + q * a.qnb1 + h * a.qnb2 + is3 * a.qnb3 + dh * (DK / NDH) * 4;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
-            const f32x4 v0 = *(const f32x4 *) (qr + (ks * 16 + hb * 8) * 4);
-            const f32x4 v1 = *(const f32x4 *) (qr + (ks * 16 + hb * 8 + 4) * 4);
+            const int  d0  = ks * 16 + hb * 8;
+            const bool qin = DKP == DK || d0 < DK;         // (DK % 8 == 0: the lane's 8 elements are inside the row or past it as a whole; past it: zeros, and no address there)
+            const int  d0c = qin ? d0 : 0;
+            const f32x4 v0 = *(const f32x4 *) (qr + d0c * 4);
+            const f32x4 v1 = *(const f32x4 *) (qr + (d0c + 4) * 4);
             fw_h8v x;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { x[e] = (_Float16) v0[e]; x[4 + e] = (_Float16) v1[e]; }
+            for (int e = 0; e < 4; ++e) { x[e] = qin ? (_Float16) v0[e] : (_Float16) 0.0f; x[4 + e] = qin ? (_Float16) v1[e] : (_Float16) 0.0f; }
             if (QLDS) Ql[ks * 64] = x; else qf[QLDS ? 0 : ks] = x;
         }
     }
@@ -301,7 +340,8 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
                 f32x4 o4;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o4[i] = acc_o[db][4 * g + i];
-                *(f32x4 *) (pr + dh * (DV / NDH) + db * 32 + 8 * g + 4 * hb) = o4;
+                const int d = dh * (DV / NDH) + db * 32 + 8 * g + 4 * hb;
+                if (DVP == DV || d < DV) *(f32x4 *) (pr + d) = o4;      // (DV % 4 == 0: a quad is inside the row or in the padding as a whole)
             }
         if (hb == 0 && dh == 0) { pr[DV] = M * 0.6931471805599453f; pr[DV + 1] = S; }
         return;
@@ -322,14 +362,18 @@ __global__ void __launch_bounds__(64 * FW_NW) k_fattn_wide(const fa_dev a, const
             f32x4 o4;
 #pragma unroll
             for (int i = 0; i < 4; ++i) o4[i] = acc_o[db][4 * g + i] * inv;
-            *(f32x4 *) (out + (dh * (DV / NDH) + db * 32 + 8 * g + 4 * hb) * 4) = o4;
+            const int d = dh * (DV / NDH) + db * 32 + 8 * g + 4 * hb;
+            if (DVP == DV || d < DV) *(f32x4 *) (out + d * 4) = o4;
         }
 }
 
 static long g_fw_launches = 0;
 long fattn_wide_launches() { return g_fw_launches; }
 
-bool fattn_wide_dims(int64_t DK, int64_t DV) { return (DK == 256 && DV == 256) || (DK == 576 && DV == 512); }
+bool fattn_wide_dims(int64_t DK, int64_t DV) {
+    if (DK == DV) return DK == 40 || DK == 72 || DK == 80 || DK == 96 || DK == 112 || DK == 256;
+    return (DK == 192 && DV == 128) || (DK == 576 && DV == 512);
+}
 int  fattn_wide_max_tiles() { return FW_MAXT; }
 
 template <int DK, int DV>
@@ -353,6 +397,12 @@ static void fw_go(const fa_dev & a0, hipStream_t st) {
 void flash_attn_ext_wide(const fa_dev & a, int DK, int DV, hipStream_t st) {
     if (DK == 256 && DV == 256) fw_go<256, 256>(a, st);
     else if (DK == 576 && DV == 512) fw_go<576, 512>(a, st);
+    else if (DK == 96  && DV == 96)  fw_go<96, 96>(a, st);
+    else if (DK == 192 && DV == 128) fw_go<192, 128>(a, st);
+    else if (DK == 80  && DV == 80)  fw_go<80, 80>(a, st);
+    else if (DK == 112 && DV == 112) fw_go<112, 112>(a, st);
+    else if (DK == 72  && DV == 72)  fw_go<72, 72>(a, st);
+    else if (DK == 40  && DV == 40)  fw_go<40, 40>(a, st);
     else { fprintf(stderr, "[mi355x] flash_attn: no wide kernel for head size %d / %d\n", DK, DV); abort(); }
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/fattn_wide_bench.py -- FLASH_ATTN_EXT at head sizes 256 / 256 (Gemma-2-9B-like: 16 heads over 8 KV heads) and 576 / 512 (DeepSeek MLA: 128 heads
-over 1 KV head): the generic kernel (option "fattn_wide" = 0, fattn_any.hip) against k_fattn_wide (= 1), in one process, alternating.
+over 1 KV head), and at 96 / 96 (Phi-3-mini: 32 / 32), 192 / 128 (DeepSeek-V2-Lite: 16 / 16), 80 / 80 and 112 / 112: the generic kernel (option "fattn_wide" = 0, fattn_any.hip) against k_fattn_wide (= 1), in one process, alternating.
 
 Single-node graphs' worth of work through the C-ABI: a graph of N FLASH_ATTN_EXT nodes, each on its own K / V set (so that decode shapes stream from HBM, not
 from the 256 MB cache), timed with the backend's timed events around graph_compute; per node time = window / N.  Per shape and option: two warm-up runs after
@@ -8,7 +8,10 @@ the option is set (it drops captured graphs), then the windows alternate 0, 1, 0
 Decode rows report the K + V bytes (read once per KV head) over the time, against the 8.0 TB/s HBM3E specification (6.29 TB/s is what a copy kernel reaches);
 prefill rows report 2 * (DK + DV) * visible (row, cell) pairs * heads FLOP over the time against 2.5 PFLOP/s dense F16.
 
-    python tools/fattn_wide_bench.py [-o profiles/fattn_wide.txt] [--only gemma|mla] [--budget-s 0.4]
+    python tools/fattn_wide_bench.py [-o profiles/fattn_wide.txt] [--only gemma,mla,phi3,v2lite,h80,h112] [--budget-s 0.4]
+
+Against another build of the library (MI355X_LIB=path: the parent commit's, say) both columns are what that build runs at the shape; for the head sizes it does not
+have on fattn_wide.hip that is its generic kernel twice ("launches per graph 0").
 """
 import argparse
 import os
@@ -35,6 +38,18 @@ SHAPES = [
     ("mla 576/512 128/1", 576, 512, 128, 1, 1, 4096, False),
     ("mla 576/512 128/1", 576, 512, 128, 1, 1, 32768, False),
     ("mla 576/512 128/1", 576, 512, 128, 1, 512, 512, True),
+    # the head sizes that are no multiple of the MFMA extents: Phi-3-mini (96, 32 heads, no GQA), DeepSeek-V2-Lite before the absorption (192 / 128, 16 heads),
+    # and 80 (Phi-2) and 112 at the prefill shape
+    ("phi3 96/96 32/32", 96, 96, 32, 32, 512, 512, True),
+    ("phi3 96/96 32/32", 96, 96, 32, 32, 1, 512, False),
+    ("phi3 96/96 32/32", 96, 96, 32, 32, 1, 4096, False),
+    ("phi3 96/96 32/32", 96, 96, 32, 32, 1, 32768, False),
+    ("v2lite 192/128 16/16", 192, 128, 16, 16, 512, 512, True),
+    ("v2lite 192/128 16/16", 192, 128, 16, 16, 1, 512, False),
+    ("v2lite 192/128 16/16", 192, 128, 16, 16, 1, 4096, False),
+    ("v2lite 192/128 16/16", 192, 128, 16, 16, 1, 32768, False),
+    ("h80 80/80 32/32", 80, 80, 32, 32, 512, 512, True),
+    ("h112 112/112 32/32", 112, 112, 32, 32, 512, 512, True),
 ]
 
 
@@ -131,7 +146,7 @@ def main():
     emit(f"# tools/fattn_wide_bench.py on {be.name()} ({be.description()}); {clocks()}")
     emit("# us per FLASH_ATTN_EXT node, median of the windows [min .. max, n]; generic = option fattn_wide 0 (fattn_any.hip), wide = 1 (fattn_wide.hip)")
     for sh in SHAPES:
-        if args.only and not sh[0].startswith(args.only):
+        if args.only and not sh[0].startswith(tuple(args.only.split(","))):
             continue
         one_shape(pkg, be, sh, args.budget_s, emit)
     emit(f"# after: {clocks()}")
