@@ -64,6 +64,8 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * "mmq_id" (1 default / 0: MUL_MAT_ID of Q4_K / Q5_K / Q6_K experts from 64 tokens on, of MXFP4 experts from 128 and of Q8_0 / Q4_0 / Q5_0 / IQ4_NL experts from 65 tokens on, runs on the
  * expert-grouped int8-MFMA kernels, csrc/kernels/mmq_id.hip -- the pairs sorted by expert on the device, one tile per (expert, 32 rows, <= 32 columns); 0 sends every node
  * to the per-pair mat-vec: the cross-check switch; process-wide),
+ * "mmq_tq" (1 default / 0: TQ1_0 / TQ2_0 weights against 9 .. 64 columns run on the int8-MFMA kernel on the packed blocks, csrc/kernels/mmq_tq.hip; 0 sends them through
+ * their F16 image: the cross-check switch; process-wide; environment MI355X_MMQ_TQ=0 is the same),
  * "mv1", "mv2", "fattn_one", "kq_staging", "batch_uploads" (cross-check switches of the decode kernels),
  * "reset_stats".  Returns 0 on success, -1 for an unknown key.
  * Environment switches read once per process (measurement / cross-check only): MI355X_GRAPHS=0, MI355X_NO_CONV_FUSE, MI355X_NO_CONCAT_TAIL, MI355X_NO_ATTN_F32,
@@ -75,7 +77,8 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
 /* counters: "graph_replays", "graph_captures", "eager_graphs", "kernels_last_graph", "mmq_tile_launches",
  * "fattn_wide_launches" (launches of the head-size 256 / 576 attention kernel, csrc/kernels/fattn_wide.hip; the merge pass of a sliced node is not counted),
  * "mmv_iq4nl_launches", "mmv_iq4xs_launches", "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches" (launches of the
- * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
+ * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_tq1_launches", "mmv_tq2_launches" (the same for TQ1_0 / TQ2_0), "mmq_tq_launches" (launches of the
+ * ternary int8-MFMA kernel, one per 2-D slice of a node) and "mmq_tq_ks" (not a counter: the K split of the most recent one, 0 before the first), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
  * "argsort_launches", "ssm_conv_launches" / "ssm_scan_launches" (SSM_CONV / SSM_SCAN: one launch per node),
  * "wkv6_launches" / "gla_launches" / "wkv7_launches" / "l2_norm_launches" (RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM: one launch per node), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
  * "mmq_id_launches" (MUL_MAT_ID nodes of K-quant experts that went through the expert-grouped launchers: the grouping and the matrix launch count as one, and such a

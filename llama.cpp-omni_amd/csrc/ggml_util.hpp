@@ -30,6 +30,8 @@ static inline type_info type_traits(int t) {
         case GGML_TYPE_IQ4_NL: return {32, 18, "iq4_nl"};
         case GGML_TYPE_IQ4_XS: return {256, 136, "iq4_xs"};
         case GGML_TYPE_MXFP4: return {32, 17, "mxfp4"};
+        case GGML_TYPE_TQ1_0: return {256, 54, "tq1_0"};
+        case GGML_TYPE_TQ2_0: return {256, 66, "tq2_0"};
         case GGML_TYPE_I8:   return {1, 1, "i8"};
         case GGML_TYPE_I16:  return {1, 2, "i16"};
         case GGML_TYPE_I32:  return {1, 4, "i32"};

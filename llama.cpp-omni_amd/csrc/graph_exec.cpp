@@ -212,6 +212,23 @@ static void mm_mmq(exec_state & s, const ggml_tensor * dst, const mm_route & r) 
         }
     }
 }
+static void mm_mmq_tq(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // 9 .. 64 columns of a TQ1_0 / TQ2_0 matrix: int8 MFMA on the blocks, one launch per (i12, i13) slice
+    const ggml_tensor * w = dst->src[0], * x = dst->src[1];
+    const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
+    const size_t img = prepare_act(s, x, r.act);
+    const double wbytes = (double) M * (double) row_size(w->type, K);
+    for (int64_t i13 = 0; i13 < ne13; ++i13) {
+        for (int64_t i12 = 0; i12 < ne12; ++i12) {
+            mmq_tq_args q;
+            q.type = w->type; q.W = (const char *) w->data + (i12 / r2) * w->nb[2] + (i13 / r3) * w->nb[3]; q.w_rs = w->nb[1];
+            q.act = (const char *) s.c->act_scratch + (size_t) ((i13 * ne12 + i12) * N) * img; q.act_cs = img;
+            q.dst = (float *) ((char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3]); q.dst_cs = dst->nb[1];
+            q.K = K; q.nrows = M; q.ncols = (int) N;
+            prof_scope ps(s, "mmq_tq", wbytes);
+            mmq_tq(q, s.st); ++s.n_kernels;
+        }
+    }
+}
 static void mm_mmv(exec_state & s, const ggml_tensor * dst, const mm_route & r) {      // the per-type mat-vec kernels, up to 8 columns per launch
     const ggml_tensor * w = dst->src[0], * x = dst->src[1];
     const int64_t K = w->ne[0], M = w->ne[1], N = x->ne[1], ne12 = x->ne[2], ne13 = x->ne[3], r2 = ne12 / w->ne[2], r3 = ne13 / w->ne[3];
@@ -249,6 +266,7 @@ void op_mul_mat(exec_state & s, const ggml_tensor * dst) {
         case MM_GEMM_ANY:       return mm_gemm_any(s, dst, r, mm_extras());
         case MM_MMV_HEADS:      return mm_mmv_heads(s, dst, r);
         case MM_MMQ:            return mm_mmq(s, dst, r);
+        case MM_MMQ_TQ:         return mm_mmq_tq(s, dst, r);
         case MM_MMV:            return mm_mmv(s, dst, r);
     }
 }

@@ -194,7 +194,7 @@ static inline void prof_drain(backend_ctx * c) {
 static const int64_t ROPE_TABLE_MIN_TOKENS = 32;
 static const int64_t GEMM_MIN_COLS = MI_MMVQ_MAX_COLS + 1;
 // Which kernel family a MUL_MAT node takes: decided once, by route_mul_mat, for the planner (supports_op), the scratch sizing and the executor (op_mul_mat).
-enum mm_path { MM_MMQ_TILE, MM_GEMM_F16_HEADS, MM_GEMM_F16, MM_GEMM_BF16, MM_GEMM_ANY, MM_MMV_HEADS, MM_MMQ, MM_MMV };
+enum mm_path { MM_MMQ_TILE, MM_GEMM_F16_HEADS, MM_GEMM_F16, MM_GEMM_BF16, MM_GEMM_ANY, MM_MMV_HEADS, MM_MMQ, MM_MMQ_TQ, MM_MMV };
 struct mm_route {
     mm_path  path;
     act_kind act;            // the image of x the path reads (prepare_act; ACT_F32 / ACT_NONE: the f32 rows themselves)
@@ -236,6 +236,7 @@ bool mm_uses_gemm_any_f16(const ggml_tensor * n);
 act_kind gemm_act_kind(const ggml_tensor * n);          // ACT_F16, or ACT_F16Q for K-quant weights (option "prefill_q8k")
 void prefill_q8k_set_mode(int m);
 void mmq_tile_set_mode(int m);
+void mmq_tq_set_mode(int m);                            // option "mmq_tq": 0 = ternary weights at 9 .. 64 columns through their F16 image
 int64_t mmq_max_cols();
 size_t graph_act_scratch_need(const ggml_cgraph * g);
 size_t graph_w_scratch_need(const ggml_cgraph * g);

@@ -29,11 +29,12 @@ bool supports_op(const ggml_tensor * op) {
                 const int t = s0->type;
                 const size_t al = (t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K) ? 16 : (t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K) ? 4 : 2;
                 if (s0->nb[1] % al != 0 || (al == 4 && ((uintptr_t) s0->data & 3) != 0)) return false;
+                if ((t == GGML_TYPE_TQ1_0 || t == GGML_TYPE_TQ2_0) && ((uintptr_t) s0->data & 1) != 0) return false;      // 54- / 66-byte blocks: rows and base 2-byte aligned, never better
             }
             // every mat-vec path (up to 8 columns per launch; F32 weights at any width) stages one activation column in LDS: a column
             // beyond 152 KiB has no kernel (e.g. attention without FLASH_ATTN_EXT past ~77k cache rows: K = n_kv) -> leave it to the CPU
             const mm_route r = route_mul_mat(op);
-            if (!r.gemm && r.path != MM_MMQ && r.path != MM_GEMM_ANY) {                  // (gemm_any stages nothing in LDS)
+            if (!r.gemm && r.path != MM_MMQ && r.path != MM_MMQ_TQ && r.path != MM_GEMM_ANY) {      // (gemm_any stages nothing in LDS; the MFMA kernels the columns' block scales only)
                 const size_t col = k == ACT_F32 ? (size_t) s0->ne[0] * 4 : act_image_bytes(k, s0->ne[0]);
                 if (col > (size_t) 152 * 1024) return false;
             }
@@ -195,7 +196,7 @@ bool supports_op(const ggml_tensor * op) {
             switch (s0->type) {
                 case GGML_TYPE_F32: case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_K: case GGML_TYPE_Q6_K:
                 case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K:
-                case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS:
+                case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS: case GGML_TYPE_TQ1_0: case GGML_TYPE_TQ2_0:
                     return s0->nb[0] == type_size(s0->type);
                 default: return false;
             }
@@ -244,6 +245,11 @@ static const mmv_row MMV_ROWS[] = {
     { GGML_TYPE_Q5_1,   ACT_Q81, mmv_q5_1,   "mmv_q51"   },
     { GGML_TYPE_Q2_K,   ACT_Q8K, mmv_q2_K,   "mmv_q2k"   },
     { GGML_TYPE_Q3_K,   ACT_Q8K, mmv_q3_K,   "mmv_q3k"   },
+    // TQ1_0 / TQ2_0 (ternary; Q8_K images): integer mat-vec kernels up to 8 columns (mmvq.hip), the int8-MFMA kernel on the blocks for 9 .. mmq_max_cols() columns
+    // (mmq_tq.hip, MM_MMQ_TQ), the F16 image beyond.  As IQ4_XS they share the Q8_K image with the K-quants and none of the K-quant launch forms (fusions, mmq,
+    // the k_mv2 engine, mmv1) takes them: those test is_kquant / the type.
+    { GGML_TYPE_TQ1_0,  ACT_Q8K, mmv_tq1_0,  "mmv_tq1"   },
+    { GGML_TYPE_TQ2_0,  ACT_Q8K, mmv_tq2_0,  "mmv_tq2"   },
     { GGML_TYPE_F16,    ACT_F16, mmv_f16,    "mmv_f16"   },
     { GGML_TYPE_F32,    ACT_F32, mmv_f32,    "mmv_f32"   },
 };
@@ -268,6 +274,18 @@ static bool mmq_takes(const ggml_tensor * n) {
     return (w->type == GGML_TYPE_Q4_K || w->type == GGML_TYPE_Q5_K || w->type == GGML_TYPE_Q6_K) && x->type == GGML_TYPE_F32 && x->ne[1] >= mmq_min_cols() && x->ne[1] <= mmq_max_cols() &&
            mmq_ok(w->type, w->ne[0], w->data, w->nb[1]) && (w->ne[2] == 1 || mmq_ok(w->type, w->ne[0], (const char *) w->data + w->nb[2], w->nb[1])) &&
            (w->ne[3] == 1 || mmq_ok(w->type, w->ne[0], (const char *) w->data + w->nb[3], w->nb[1]));
+}
+// TQ1_0 / TQ2_0 weights against 9 .. mmq_max_cols() columns: the int8-MFMA kernel on the packed blocks and the Q8_K images (mmq_tq.hip) -- 0.21 / 0.26 bytes per weight
+// where the F16 image is 2.  Both bounds are inherited from the other formats (the mat-vec forms end at 8 columns, the K-quant MFMA kernel at 64): nobody has measured
+// them for ternary weights.  Batched nodes (ne[2] * ne[3] > 1) take the path too: the executor walks the slices on the host, one launch each, as it does for MM_MMQ.
+static int g_mmq_tq = -1;                                     // option "mmq_tq": -1 = MI355X_MMQ_TQ decides (default on), 0 off (the cross-check switch: the F16 image), 1 on
+void mmq_tq_set_mode(int m) { g_mmq_tq = m; }
+static bool mmq_tq_takes(const ggml_tensor * n) {
+    static const int env = getenv("MI355X_MMQ_TQ") ? atoi(getenv("MI355X_MMQ_TQ")) : 1;
+    const ggml_tensor * w = n->src[0], * x = n->src[1];
+    if ((w->type != GGML_TYPE_TQ1_0 && w->type != GGML_TYPE_TQ2_0) || !(g_mmq_tq >= 0 ? g_mmq_tq : env)) return false;
+    if (x->type != GGML_TYPE_F32 || x->ne[1] <= MI_MMVQ_MAX_COLS || x->ne[1] > mmq_max_cols() || x->ne[1] > INT32_MAX) return false;
+    return mmq_tq_ok(w->type, w->ne[0], w->ne[1], w->data, w->nb[1]) && (w->ne[2] == 1 || w->nb[2] % 2 == 0) && (w->ne[3] == 1 || w->nb[3] % 2 == 0);
 }
 // Q4_K weights against a prefill ubatch (more than mmq_max_cols() columns): the tiled int8-MFMA kernel on the blocks themselves and the Q8_K-quantised
 // activations -- the oracle's integers (mmq_tile.hip).  A sub-case of the F16 GEMM (mm_uses_gemm): the grouping / residual / split-K machinery of the GEMM path serves it.
@@ -300,7 +318,7 @@ static bool gemm_f16_takes(const ggml_tensor * n) {
     const ggml_tensor * w = n->src[0], * x = n->src[1];
     static const bool no_gemm = getenv("MI355X_NO_GEMM") != nullptr;
     if (x->ne[1] < GEMM_MIN_COLS || no_gemm) return false;
-    if (mmq_takes(n)) return false;
+    if (mmq_takes(n) || mmq_tq_takes(n)) return false;
     if (!mmv_row_for(w->type) || w->type == GGML_TYPE_F32) return false;         // F16 and every block format, through its F16 image
     const int64_t K = w->ne[0];
     if (K % 32 != 0) return false;
@@ -342,6 +360,7 @@ mm_route route_mul_mat(const ggml_tensor * n) {
     if ((w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32) && nbatch > 1 && N <= MI_MMVQ_MAX_COLS && nbatch <= 65535 &&
         (r.act != ACT_F32 || x->ne[3] == 1 || x->nb[3] == (size_t) x->ne[2] * x->nb[2])) { r.path = MM_MMV_HEADS; return r; }
     if (mmq_takes(n)) { r.path = MM_MMQ; return r; }                                  // 6 .. 64 columns of a K-quant matrix: int8 MFMA, 32 columns per launch
+    if (mmq_tq_takes(n)) { r.path = MM_MMQ_TQ; return r; }                            // 9 .. 64 columns of a ternary matrix: int8 MFMA on the blocks, every column in one launch
     return r;                                                                         // the type's own mat-vec kernels, on the blocks (w_image only ever with the GEMM)
 }
 // The same for MUL_MAT_ID (as [K, M, n_expert], b [K, 1 | n_ids, T] f32, ids [n_ids, T] i32 -> [M, n_ids, T]).  Two paths:
@@ -357,7 +376,7 @@ mm_route route_mul_mat(const ggml_tensor * n) {
 //              for the rest);
 //   MM_ID_MMQ  Q8_0 / Q4_0 / Q5_0 / IQ4_NL (a 32-weight block against the Q8_0 image, no min term) from mmq_id_blocks_min_tokens() tokens on: the grouping, then one int8
 //              MFMA per block (mmq_id.hip, the MXFP4 body with another block decoder).  Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_XS experts stay per-pair at every token count.
-// F16 / F32 / BF16 experts have no kernel with the id indirection: refused, they stay on the CPU.
+// F16 / F32 / BF16 experts have no kernel with the id indirection: refused, they stay on the CPU.  So are TQ1_0 / TQ2_0 experts (no id form of their kernels yet).
 static int g_mmq_id = -1;                                     // option "mmq_id": -1 = MI355X_MMQ_ID decides (default on), 0 off (the cross-check switch), 1 on
 void mmq_id_set_mode(int m) { g_mmq_id = m; }
 int64_t mmq_id_mxfp4_min_tokens() {

@@ -47,9 +47,11 @@ void mmv_q4_1(const mmv_args & a, hipStream_t st);    // Q4_1 / Q5_1 x Q8_1 imag
 void mmv_q5_1(const mmv_args & a, hipStream_t st);
 void mmv_q2_K(const mmv_args & a, hipStream_t st);    // Q2_K / Q3_K x Q8_K images (vec_dot_q2_K_q8_K / _q3_K_q8_K integers; K % 256 == 0, rows 4- / 2-byte aligned)
 void mmv_q3_K(const mmv_args & a, hipStream_t st);
-// the nine block formats above share one kernel frame (mmvq.hip); kernel launches so far per form (stats "mmv_iq4nl_launches", "mmv_iq4xs_launches",
-// "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches")
-enum { MMV_FORM_Q8_0 = 0, MMV_FORM_Q4_0, MMV_FORM_Q5_0, MMV_FORM_IQ4_NL, MMV_FORM_IQ4_XS, MMV_FORM_Q4_1, MMV_FORM_Q5_1, MMV_FORM_Q2_K, MMV_FORM_Q3_K, MMV_FORM_COUNT };
+void mmv_tq1_0(const mmv_args & a, hipStream_t st);   // TQ1_0 / TQ2_0 (ternary) x Q8_K images (vec_dot_tq1_0_q8_K / _tq2_0_q8_K integers; K % 256 == 0, rows and base 2-byte aligned)
+void mmv_tq2_0(const mmv_args & a, hipStream_t st);
+// the eleven block formats above share one kernel frame (mmvq.hip); kernel launches so far per form (stats "mmv_iq4nl_launches", "mmv_iq4xs_launches",
+// "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches", "mmv_tq1_launches", "mmv_tq2_launches")
+enum { MMV_FORM_Q8_0 = 0, MMV_FORM_Q4_0, MMV_FORM_Q5_0, MMV_FORM_IQ4_NL, MMV_FORM_IQ4_XS, MMV_FORM_Q4_1, MMV_FORM_Q5_1, MMV_FORM_Q2_K, MMV_FORM_Q3_K, MMV_FORM_TQ1_0, MMV_FORM_TQ2_0, MMV_FORM_COUNT };
 long mmv_blocks_launches(int form);
 void mmv_f16 (const mmv_args & a, hipStream_t st);   // act = f16 rows
 void mmv_f32 (const mmv_args & a, hipStream_t st);   // W f32, act = f32 rows
@@ -135,6 +137,13 @@ struct mmq_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_
 struct mmq_args { mmq_mat m[3]; int nmat; const void * act; size_t act_cs; int64_t K; int ncols; };
 bool mmq_ok(int type, int64_t K, const void * W, size_t w_rs);
 void mmq_kquant(const mmq_args & a, hipStream_t st);
+// ---- TQ1_0 / TQ2_0 (ternary) weights against 9 .. 64 activation columns on the int8 matrix cores (mmq_tq.hip): the packed blocks against the Q8_K images, eight
+// MFMAs into one i32 accumulator per 256-weight block, one float epilogue per block.  One launch covers every column: grid y walks slices of 32.
+struct mmq_tq_args { int type; const void * W; size_t w_rs; const void * act; size_t act_cs; float * dst; size_t dst_cs; int64_t K, nrows; int ncols; };
+bool mmq_tq_ok(int type, int64_t K, int64_t nrows, const void * W, size_t w_rs);      // K a multiple of 256, rows and base 2-byte aligned, the columns' scales + the fold area within 64 KiB of LDS
+void mmq_tq(const mmq_tq_args & a, hipStream_t st);
+struct mmq_tq_stat { long launches; int ks; };          // launches so far (stat "mmq_tq_launches"), the K split of the most recent one ("mmq_tq_ks", 0: none yet)
+mmq_tq_stat mmq_tq_stats();
 // ---- MUL_MAT_ID against many tokens on the int8 matrix cores (mmq_id.hip): the pairs grouped by expert on the device (k_moe_group: pair list, tile table and tile count
 // into `scratch`, moe_group_bytes), then one workgroup per (expert, 32-row tile, <= 32-column slice), columns read and results stored through the pair list (k_mmq_id).
 // Nothing reads the ids on the host.  Three families of expert types, `m` as for the family's per-pair mat-vec:

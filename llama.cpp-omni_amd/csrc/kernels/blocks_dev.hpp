@@ -1,5 +1,5 @@
 // blocks_dev.hpp -- what the mat-vec Forms of the 32-weight block formats (mmvq.hip) and the expert-grouped int8-MFMA kernel on the same blocks (mmq_id.hip)
-// share: the fifth-bit spread of Q5_0 / Q5_1 and the IQ4_NL table look-up.
+// share: the fifth-bit spread of Q5_0 / Q5_1 and the IQ4_NL table look-up; and, with the ternary int8-MFMA kernel (mmq_tq.hip), the base-3 digits of TQ1_0.
 #pragma once
 #include "../kernels.hpp"
 
@@ -19,6 +19,14 @@ static __device__ __forceinline__ uint32_t iq4nl_lut4(uint32_t n) {      // n: f
     uint32_t m = (n >> 3) & 0x01010101u;
     m = (m << 8) - m;                                                     // 0xFF in every byte whose index is >= 8 (no borrow crosses a byte)
     return (hi & m) | (lo & ~m);
+}
+
+// TQ1_0 (ternary weights, five per byte in base 3; ggml-quants.c:2215): four base-3 digits at once: digit n of the four bytes of `dw` is (((uint8) (b * 3^n)) * 3) >> 8.  Even and odd bytes go into 16-bit lanes (255 * 243 < 65536
+// and 255 * 3 < 65536: no product leaves its lane; every operand is below 2^24, so the multiplies are v_mul_u32_u24), results 0 .. 2, one per byte
+static __device__ __forceinline__ uint32_t tq1_digits(uint32_t dw, uint32_t pow3) {
+    const uint32_t ev = __umul24(__umul24(dw & 0x00ff00ffu, pow3) & 0x00ff00ffu, 3u);            // bits 8, 9 of a lane: the digit of byte 0 / byte 2
+    const uint32_t od = __umul24(__umul24((dw >> 8) & 0x00ff00ffu, pow3) & 0x00ff00ffu, 3u);     // the same of byte 1 / byte 3 -- already where the byte sits
+    return ((ev >> 8) & 0x00030003u) | (od & 0x03000300u);
 }
 
 } // namespace mi

@@ -92,8 +92,8 @@ __global__ void __launch_bounds__(256) k_dequant_q80(const char * __restrict__ s
     (void) nb;
 }
 
-// ---- the other block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q5_K / IQ4_NL / IQ4_XS): one element at a time, the float operations of
-// dequantize_row_q4_0 :307, _q4_1 :327, _q5_0 :348, _q5_1 :374, _q2_K :784, _q3_K :1128, _q5_K :1554, _iq4_nl :2512, _iq4_xs :2530 (ggml-quants.c) in the same order.
+// ---- the other block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K / Q5_K / IQ4_NL / IQ4_XS / TQ1_0 / TQ2_0): one element at a time, the float operations of
+// dequantize_row_q4_0 :307, _q4_1 :327, _q5_0 :348, _q5_1 :374, _q2_K :784, _q3_K :1128, _q5_K :1554, _iq4_nl :2512, _iq4_xs :2530, _tq1_0 :2215, _tq2_0 :2254 (ggml-quants.c) in the same order.
 // MUL_MAT from 9 columns on runs on the (resident) F16 image this function fills (mat-vecs read the blocks: mmvq.hip), GET_ROWS gathers through it.
 static __device__ __forceinline__ float h2f_at(const uint8_t * p) { return h2f((uint16_t) (p[0] | (p[1] << 8))); }
 __constant__ int8_t kvalues_iq4nl_dev[16] = { -127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113 };     // ggml-common.h:1088-1090
@@ -166,6 +166,24 @@ static __device__ float dq_elem_other(int type, const char * row, int64_t e) {
             const uint8_t q = b[8 + 16 * ib + (l & 15)];
             return dl * (float) kvalues_iq4nl_dev[l < 16 ? (q & 0xF) : (q >> 4)];
         }
+        case GGML_TYPE_TQ1_0: {                                       // qs[48] qh[4] d: five base-3 digits per qs byte, four per qh byte (dequantize_row_tq1_0 :2215)
+            const uint8_t * b = (const uint8_t *) row + (e / 256) * 54;
+            const int w = (int) (e % 256);
+            int n, at;                                                // digit n of byte `at`: qs[0..31] five planes of 32, qs[32..47] five planes of 16, qh four planes of 4
+            if (w < 160)      { n = w >> 5; at = w & 31; }
+            else if (w < 240) { n = (w - 160) >> 4; at = 32 + ((w - 160) & 15); }
+            else              { n = (w - 240) >> 2; at = 48 + ((w - 240) & 3); }
+            const int pow3 = n == 0 ? 1 : n == 1 ? 3 : n == 2 ? 9 : n == 3 ? 27 : 81;
+            const uint8_t q = (uint8_t) (b[at] * pow3);
+            const int xi = ((int) q * 3) >> 8;
+            return (float) (xi - 1) * h2f_at(b + 52);
+        }
+        case GGML_TYPE_TQ2_0: {                                       // qs[64] d: two groups of 32 bytes, plane l = bits 2l, 2l + 1 (dequantize_row_tq2_0 :2254)
+            const uint8_t * b = (const uint8_t *) row + (e / 256) * 66;
+            const int w = (int) (e % 256), j = w >> 7, l = (w >> 5) & 3, m = w & 31;
+            const int q = (b[32 * j + m] >> (2 * l)) & 3;
+            return (float) (q - 1) * h2f_at(b + 64);
+        }
         default: return 0.0f;
     }
 }
@@ -188,7 +206,7 @@ static void dequant_rows_t(int type, const void * src, size_t src_rs, T * dst, s
             k_dequant_q6k<T><<<dim3((unsigned) ((nthreads + 255) / 256)), dim3(256), 0, st>>>((const char *) src, src_rs, (char *) dst, dst_rs, K, nrows); break;
         case GGML_TYPE_Q8_0: nthreads = nrows * K;
             k_dequant_q80<T><<<dim3((unsigned) ((nthreads + 255) / 256)), dim3(256), 0, st>>>((const char *) src, src_rs, (char *) dst, dst_rs, K, nrows); break;
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS:
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS: case GGML_TYPE_TQ1_0: case GGML_TYPE_TQ2_0:
             nthreads = nrows * K;
             k_dequant_other<T><<<dim3((unsigned) ((nthreads + 255) / 256)), dim3(256), 0, st>>>(type, (const char *) src, src_rs, (char *) dst, dst_rs, K, nrows); break;
         default: fprintf(stderr, "[mi355x] dequant_rows: unsupported type %d\n", type); abort();
@@ -1287,7 +1305,7 @@ void get_rows(const tdesc & src, int src_type, const tdesc & idx, const tdesc & 
         case GGML_TYPE_F16: k_get_rows<uint16_t><<<grid, dim3(256), 0, st>>>(s, i, d); break;
         case GGML_TYPE_BF16: k_get_rows<bf16_t><<<grid, dim3(256), 0, st>>>(s, i, d); break;
         case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_K: case GGML_TYPE_Q6_K:
-        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS:
+        case GGML_TYPE_Q4_0: case GGML_TYPE_Q4_1: case GGML_TYPE_Q5_0: case GGML_TYPE_Q5_1: case GGML_TYPE_Q2_K: case GGML_TYPE_Q3_K: case GGML_TYPE_Q5_K: case GGML_TYPE_IQ4_NL: case GGML_TYPE_IQ4_XS: case GGML_TYPE_TQ1_0: case GGML_TYPE_TQ2_0:
             k_get_rows_q<<<grid, dim3(256), 0, st>>>(src_type, s, i, d); break;
         default: fprintf(stderr, "[mi355x] get_rows: unsupported type %d\n", src_type); abort();
     }

@@ -1,4 +1,4 @@
-// mmvq.hip -- weight-streaming mat-vec kernels for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_NL / IQ4_XS / F16 / F32 weights (gfx950, wave64); Q4_K / Q5_K / Q6_K live in mmvk.hip.
+// mmvq.hip -- weight-streaming mat-vec kernels for Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_NL / IQ4_XS / TQ1_0 / TQ2_0 / F16 / F32 weights (gfx950, wave64); Q4_K / Q5_K / Q6_K live in mmvk.hip.
 //
 // Computes what the reference CPU backend computes in ggml_compute_forward_mul_mat
 // (ggml-cpu/ggml-cpu.c:1210-1402) for ne11 <= 8: every output is one `vec_dot` of a quantised weight
@@ -587,6 +587,117 @@ struct q3k_form {
 };
 
 // =================================================================================================
+// TQ1_0 / TQ2_0 (ternary) weights x Q8_K activations.  reference: ggml_vec_dot_tq1_0_q8_K / _tq2_0_q8_K (ggml-cpu/quants.c:335 / :387): ONE integer sum over
+// the 256 weights of a block and one float multiply,
+//   sumf += (float) sum_e (x_e - 1) * y.qs[e] * (d_x * d_y)
+// The - 1 is taken out of the dot products: sum x_e * y_e - sum y_e, the second sum from the image's bsums (16 activations each) -- all exact integers, the
+// TQ2_0 field 3 (weight + 2) included.  Four lanes per block; each converts its part's integer, which the reference converts once per block.
+// =================================================================================================
+// (tq1_digits, four base-3 digits of a dword at once: blocks_dev.hpp)
+
+// TQ2_0: 66-B block {qs[64], f16 d} (ggml-common.h:252), 2-byte aligned.  qs is two groups of 32 bytes; plane l (bits 2l, 2l + 1) of group j is weights
+// 128 j + 32 l .. + 31.  Lane quarter qq owns qs bytes 16 qq .. + 15 (one 16-byte load): group j = qq >> 1, byte half h = qq & 1, so plane l of its bytes
+// is weights 128 j + 32 l + 16 h .. + 15 -- sixteen consecutive activation bytes, and bsums[8 j + 2 l + h] is their sum.
+struct tq2_form {
+    static constexpr int LANES = 4, BYTES = 66, LOG2W = 8, ID = MMV_FORM_TQ2_0;
+    static constexpr int U(int) { return 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q8k_image_bytes(K); }
+    typedef u32x4 __attribute__((aligned(2))) u32x4a2;
+    struct regs { u32x4 q; uint32_t dw; };
+    struct row  { uint32_t w[4][4]; float dx; };
+    struct col  { u32x4 a[4]; int ysum; float yd; };
+    static __device__ __forceinline__ regs load(const char * bp, int qq) { return { *(const u32x4a2 *) (bp + 16 * qq), (uint32_t) *(const uint16_t *) (bp + 64) }; }
+    static __device__ __forceinline__ row decode(const regs & x, int) {
+        row r;
+        r.dx = h2f((uint16_t) x.dw);
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r.w[l][k] = (x.q[k] >> (2 * l)) & 0x03030303u;
+        return r;
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int qq, int K, int) {
+        const int j = qq >> 1, h = qq & 1;
+        col y;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) y.a[l] = *(const u32x4 *) (im + (size_t) ib * 256 + 128 * j + 32 * l + 16 * h);
+        const u32x4 bs = *(const u32x4 *) (im + K + ib * 32 + 16 * j);          // bsums[8j .. 8j+7]: plane l of this lane is element 2l + h
+        y.ysum = 0;
+#pragma unroll
+        for (int l = 0; l < 4; ++l) y.ysum += ((int) (bs[l] << (16 - 16 * h))) >> 16;
+        y.yd = *(const float *) (im + K + K / 8 + ib * 4);
+        return y;
+    }
+    static __device__ __forceinline__ float term(const row & r, const col & y, int) {
+        int s = -y.ysum;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s = dot4(r.w[l][k], y.a[l][k], s);
+        return (float) s * (r.dx * y.yd);
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum(v); }
+};
+
+// TQ1_0: 54-B block {qs[48], qh[4], f16 d} (ggml-common.h:244), 2-byte aligned.  Digit n of qs[0..31] is weight 32 n + m, of qs[32..47] weight 160 + 16 n + m,
+// of qh[0..3] weight 240 + 4 n + j.  Lane parts 0 .. 2 own 16 bytes each (qs 0..15, 16..31, 32..47: one 16-byte load, five digits); part 3 owns the qh dword,
+// whose four digits are the four dwords of ONE group of sixteen weights (240 .. 255).  Every part's plane is sixteen consecutive activation bytes at
+//   32 n (part 0), 32 n + 16 (part 1), 160 + 16 n (part 2), 240 (part 3)                                                       -- one bsum each.
+// Part 3 decodes its unused planes 1 .. 4 to zero weights and adds no bsum for them.
+struct tq1_form {
+    static constexpr int LANES = 4, BYTES = 54, LOG2W = 8, ID = MMV_FORM_TQ1_0;
+    static constexpr int U(int) { return 1; }
+    MI_HD static size_t image_bytes(int64_t K) { return q8k_image_bytes(K); }
+    typedef u32x4 __attribute__((aligned(2))) u32x4a2;
+    typedef uint32_t __attribute__((aligned(2))) u32a2;
+    struct regs { u32x4 q; uint32_t qh, dw; };
+    struct row  { uint32_t w[5][4]; float dx; };
+    struct col  { u32x4 a[5]; int ysum; float yd; };
+    static __device__ __forceinline__ int act_off(int p, int n) { return p == 3 ? 240 : p == 2 ? 160 + 16 * n : 32 * n + 16 * p; }
+    static __device__ __forceinline__ regs load(const char * bp, int p) {
+        return { *(const u32x4a2 *) (bp + 16 * (p < 2 ? p : 2)), *(const u32a2 *) (bp + 48), (uint32_t) *(const uint16_t *) (bp + 52) };
+    }
+    static __device__ __forceinline__ row decode(const regs & x, int p) {
+        const bool p3 = p == 3;
+        row r;
+        r.dx = h2f((uint16_t) x.dw);
+        uint32_t pw = 1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { r.w[0][k] = tq1_digits(p3 ? x.qh : x.q[k], p3 ? pw : 1u); pw *= 3; }
+        pw = 3;
+#pragma unroll
+        for (int n = 1; n < 5; ++n) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r.w[n][k] = p3 ? 0u : tq1_digits(x.q[k], pw);
+            pw *= 3;
+        }
+        return r;
+    }
+    static __device__ __forceinline__ col read(const char * im, int ib, int p, int K, int) {
+        col y;
+        y.ysum = 0;
+#pragma unroll
+        for (int n = 0; n < 5; ++n) {
+            const int off = act_off(p, n);
+            y.a[n] = *(const u32x4 *) (im + (size_t) ib * 256 + off);
+            const int bs = *(const int16_t *) (im + K + ib * 32 + (off >> 4) * 2);
+            y.ysum += (n == 0 || p != 3) ? bs : 0;
+        }
+        y.yd = *(const float *) (im + K + K / 8 + ib * 4);
+        return y;
+    }
+    static __device__ __forceinline__ float term(const row & r, const col & y, int) {
+        int s = -y.ysum;
+#pragma unroll
+        for (int n = 0; n < 5; ++n)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s = dot4(r.w[n][k], y.a[n][k], s);
+        return (float) s * (r.dx * y.yd);
+    }
+    static __device__ __forceinline__ float reduce(float v) { return wave_sum(v); }
+};
+
+// =================================================================================================
 // F16 / F32 weights: each lane consumes 16 B (8 halfs / 4 floats) per step; activations (f16 rows for F16
 // weights, as the reference rounds src1 to the F16 vec_dot_type; f32 rows for F32 weights) live in LDS.
 // =================================================================================================
@@ -846,6 +957,8 @@ void mmv_q4_1(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q41_form
 void mmv_q5_1(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q41_form<true>>(a, st); }
 void mmv_q2_K(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q2k_form>(a, st); }
 void mmv_q3_K(const mmv_args & a, hipStream_t st)   { mmv_blocks_launch<q3k_form>(a, st); }
+void mmv_tq1_0(const mmv_args & a, hipStream_t st)  { mmv_blocks_launch<tq1_form>(a, st); }
+void mmv_tq2_0(const mmv_args & a, hipStream_t st)  { mmv_blocks_launch<tq2_form>(a, st); }
 
 // ---- MUL_MAT_ID on experts of the nine block formats (k_mmv_blocks_id): one launch per node, grid sized as mmv_id_kquant (mmvk.hip)
 static long g_mmv_id_blocks_launches = 0;

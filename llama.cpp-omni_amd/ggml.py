@@ -20,6 +20,7 @@ GGML_TYPE_F32, GGML_TYPE_F16, GGML_TYPE_Q8_0 = 0, 1, 8
 GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_K = 12, 14, 15
 GGML_TYPE_I32, GGML_TYPE_I64 = 26, 27
 GGML_TYPE_IQ4_NL, GGML_TYPE_IQ4_XS = 20, 23
+GGML_TYPE_TQ1_0, GGML_TYPE_TQ2_0 = 34, 35     # ternary: 256 weights in 54 bytes {qs[48] (five per byte, base 3), qh[4] (four per byte), f16 d} / 66 bytes {qs[64] (2 bits each), f16 d}
 GGML_TYPE_MXFP4 = 39                      # {uint8 e (E8M0); uint8 qs[16]}: 32 weights in 17 bytes (ggml-common.h block_mxfp4)
 GGML_ROPE_TYPE_NORMAL, GGML_ROPE_TYPE_NEOX = 0, 2
 GGML_ROPE_TYPE_MROPE, GGML_ROPE_TYPE_VISION = 8, 24      # ggml_rope_multi: four position rows and sections[4]
@@ -61,6 +62,7 @@ _TRAITS = {  # type -> (block elements, block bytes, numpy dtype or None)
     2: (32, 18, None), 3: (32, 20, None), 6: (32, 22, None), 7: (32, 24, None),      # Q4_0 Q4_1 Q5_0 Q5_1
     10: (256, 84, None), 11: (256, 110, None), 13: (256, 176, None),                # Q2_K Q3_K Q5_K
     GGML_TYPE_IQ4_NL: (32, 18, None), GGML_TYPE_IQ4_XS: (256, 136, None), GGML_TYPE_MXFP4: (32, 17, None),
+    GGML_TYPE_TQ1_0: (256, 54, None), GGML_TYPE_TQ2_0: (256, 66, None),
     30: (1, 2, np.uint16),                                                          # BF16 (as raw 16-bit words)
 }
 

@@ -11,7 +11,7 @@ import math
 import numpy as np
 
 from .ggml import (GGML_BACKEND_BUFFER_USAGE_WEIGHTS, GGML_ROPE_TYPE_NEOX, GGML_TYPE_F16, GGML_TYPE_F32, GGML_TYPE_I32, GGML_TYPE_I64, GGML_TYPE_IQ4_NL,
-                   GGML_TYPE_IQ4_XS, GGML_TYPE_MXFP4, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_0, Context, row_size)
+                   GGML_TYPE_IQ4_XS, GGML_TYPE_MXFP4, GGML_TYPE_Q4_K, GGML_TYPE_Q6_K, GGML_TYPE_Q8_0, GGML_TYPE_TQ1_0, GGML_TYPE_TQ2_0, Context, row_size)
 
 QWEN3_8B = dict(n_embd=4096, n_layer=36, n_head=32, n_head_kv=8, head_dim=128, n_ff=12288, n_vocab=151936,
                 rms_eps=1e-6, rope_base=1e6, n_ctx_orig=40960)
@@ -169,6 +169,13 @@ def random_blocks(rng, ty, nrows, K, std=0.02):
         blk[..., 0] = np.clip(e0 + rng.integers(-1, 2, size=(nrows, nb)), 0, 254).astype(np.uint8)
         blk[..., 1:] = rng.integers(0, 256, size=(nrows, nb, 16), dtype=np.uint8)
         return blk.reshape(nrows, nb * 17)
+    if ty in (GGML_TYPE_TQ1_0, GGML_TYPE_TQ2_0):             # {qs[48], qh[4], d} / {qs[64], d}: value = (q - 1) * d.  Every byte decodes: TQ1_0 digits to 0..2, TQ2_0 fields to 0..3
+        nb, bs = K // 256, (54 if ty == GGML_TYPE_TQ1_0 else 66)       # (a TQ2_0 field of 3 is the weight +2: kept, it pins the arithmetic to (q & 3) - 1); std ~ 0.82 d / 1.12 d
+        blk = np.empty((nrows, nb, bs), dtype=np.uint8)
+        d = (std / (0.82 if ty == GGML_TYPE_TQ1_0 else 1.12)) * rng.uniform(0.5, 1.5, size=(nrows, nb)).astype(np.float32)
+        blk[..., :bs - 2] = rng.integers(0, 256, size=(nrows, nb, bs - 2), dtype=np.uint8)
+        blk[..., bs - 2:] = _f16_bits(d)[..., None].view(np.uint8).reshape(nrows, nb, 2)
+        return blk.reshape(nrows, nb * bs)
     raise ValueError(ty)
 
 

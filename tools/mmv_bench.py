@@ -4,7 +4,7 @@ C-ABI.  One cgraph holds N MUL_MAT nodes over N *distinct* weight tensors (N x b
 Infinity Cache cannot serve re-reads) that share one activation vector; the graph is replayed a few times and timed
 with HIP events on the backend's stream.  Reports us per mat-vec and algorithmic GB/s (weight bytes / time).
 
-usage: python tools/mmv_bench.py [--types q4_K,q6_K] [--shapes 4096x4096,...] [--reps 5] [--ncols 1] [--mv1 0] [--weights-buffer]
+usage: python tools/mmv_bench.py [--types q4_K,q6_K] [--shapes 4096x4096,...] [--reps 5] [--ncols 1] [--mv1 0] [--mmq-tq 0] [--weights-buffer]
 """
 import argparse
 import os
@@ -15,7 +15,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import load_pkg  # noqa: E402
 
-TYPES = {"q4_K": 12, "q6_K": 14, "q8_0": 8, "f16": 1, "q4_0": 2, "q5_0": 6, "q5_K": 13, "iq4_nl": 20, "iq4_xs": 23, "q4_1": 3, "q5_1": 7, "q2_K": 10, "q3_K": 11}
+TYPES = {"q4_K": 12, "q6_K": 14, "q8_0": 8, "f16": 1, "q4_0": 2, "q5_0": 6, "q5_K": 13, "iq4_nl": 20, "iq4_xs": 23, "q4_1": 3, "q5_1": 7, "q2_K": 10, "q3_K": 11, "tq1_0": 34, "tq2_0": 35}
 
 
 def main():
@@ -27,6 +27,7 @@ def main():
     ap.add_argument("--min-mib", type=int, default=768)
     ap.add_argument("--pair", action="store_true")
     ap.add_argument("--mv1", type=int, default=-1, help="option mv1 (0: Q4_K / Q6_K single columns on the register-load kernels of mmvk.hip instead of the batch-1 forms)")
+    ap.add_argument("--mmq-tq", type=int, default=-1, help="option mmq_tq (0: TQ1_0 / TQ2_0 weights at 9 .. 64 columns through their F16 image instead of the int8-MFMA kernel of mmq_tq.hip)")
     ap.add_argument("--weights-buffer", action="store_true",
                     help="weights in a buffer of their own marked GGML_BACKEND_BUFFER_USAGE_WEIGHTS, as libllama's model buffers: a path that reads a resident F16 image builds it once, in the warm-up")
     args = ap.parse_args()
@@ -36,6 +37,8 @@ def main():
     be = pkg.backend(0)
     if args.mv1 >= 0:
         be.set_option("mv1", args.mv1)
+    if args.mmq_tq >= 0:
+        be.set_option("mmq_tq", args.mmq_tq)
     rng = np.random.default_rng(0)
     for tname in args.types.split(","):
         ty = TYPES[tname]
