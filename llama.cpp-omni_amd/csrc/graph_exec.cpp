@@ -14,6 +14,14 @@ size_t prepare_act(exec_state & s, const ggml_tensor * x, act_kind kind) {
     if (kind == ACT_Q8KT && (ne12 != 1 || ne13 != 1 || x->type != GGML_TYPE_F32)) { fprintf(stderr, "[mi355x] prepare_act: the block-major Q8_K image takes one 2-D f32 activation\n"); abort(); }
     if (s.act.holds(x, kind)) return img;
     void * const act = act_begin(s);
+    if (kind == ACT_BF16) {                                              // MUL_MAT_ID on BF16 experts: b [K, b_ne1, T] f32, every column in one launch whatever its strides
+        if (x->type != GGML_TYPE_F32 || ne13 != 1) { fprintf(stderr, "[mi355x] prepare_act: the bf16 image takes one 3-D f32 activation\n"); abort(); }
+        prof_scope ps(s, "act_convert", 0);
+        convert_f32_bf16_rows((const float *) x->data, x->nb[1], x->nb[2], N, ne12, (uint16_t *) act, img, K, s.st);
+        ++s.n_kernels;
+        s.act.seed(x, kind);
+        return img;
+    }
     auto conv = [&](const float * src, size_t xs, void * out, int64_t rows) {
         if      (kind == ACT_Q8K) quantize_q8k_image(src, xs, out, K, rows, s.st);
         else if (kind == ACT_Q8KT) quantize_q8k_tile_image(src, xs, out, K, rows, s.st);
@@ -514,7 +522,8 @@ void compute_node(exec_state & s, int i) {
         case GGML_OP_MUL_MAT_ID: {                                       // expert mat-vecs, one (slot, token) pair per workgroup column (mmvk.hip k_mmv_id) -- or, K-quant experts
                                                                          // against a prefill ubatch, the pairs grouped by expert for the int8-MFMA kernel (mmq_id.hip);
                                                                          // MXFP4 experts: mmv_mxfp4.hip / mmq_id.hip; the nine block forms: mmvq.hip
-                                                                         // k_mmv_blocks_id / (Q8_0, Q4_0, Q5_0, IQ4_NL) mmq_id.hip
+                                                                         // k_mmv_blocks_id / (Q8_0, Q4_0, Q5_0, IQ4_NL) mmq_id.hip; BF16 / F32 experts:
+                                                                         // mm_id_f.hip k_mmv_id_f / (BF16) the grouped bf16-MFMA kernel k_mm_id_16
             const ggml_tensor * as = n->src[0], * b = n->src[1], * ids = n->src[2];
             const mm_id_route r = route_mul_mat_id(n);
             if (!r.ok) { log_msg(GGML_LOG_LEVEL_ERROR, "[mi355x] graph_compute: MUL_MAT_ID %s reached the backend but has no kernel -- supports_op bug\n", n->name); abort(); }
@@ -526,6 +535,7 @@ void compute_node(exec_state & s, int i) {
             a.ids = ids->data; a.ids_nb0 = ids->nb[0]; a.ids_nb1 = ids->nb[1]; a.n_ids = ids->ne[0]; a.n_tokens = ids->ne[1];
             a.act = s.c->act_scratch; a.b_ne1 = b->ne[1];
             a.dst = (float *) n->data; a.dst_nb1 = n->nb[1]; a.dst_nb2 = n->nb[2]; a.K = as->ne[0]; a.nrows = as->ne[1];
+            if (r.act == ACT_F32) { a.act = b->data; a.b_nb1 = b->nb[1]; a.b_nb2 = b->nb[2]; }      // F32 experts: b's columns where they lie
             switch (r.path) {
                 case MM_ID_MMQ: {                                         // (bytes: every expert's matrix once -- the floor of a launch that touches them all)
                     static const char * const scope[MMQ_ID_FAMILIES] = { "mmq_id", "mmq_id_mxfp4", "mmq_id_blocks" };
@@ -534,9 +544,16 @@ void compute_node(exec_state & s, int i) {
                     s.n_kernels += 2;                                     // the grouping launch and the matrix launch
                     break;
                 }
+                case MM_ID_BF16: {                                        // (bytes: as MM_ID_MMQ)
+                    prof_scope ps(s, "mm_id_bf16", (double) std::min(as->ne[2], ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
+                    mm_id_bf16({ a, s.c->moe_scratch, s.c->moe_scratch_bytes }, s.st);
+                    s.n_kernels += 2;                                     // the grouping launch and the matrix launch
+                    break;
+                }
                 case MM_ID_MMV: {
-                    prof_scope ps(s, "mmv_id", (double) (ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
-                    if (as->type == GGML_TYPE_MXFP4) mmv_id_mxfp4(a, s.st);
+                    prof_scope ps(s, r.act == ACT_BF16 || r.act == ACT_F32 ? "mmv_id_f" : "mmv_id", (double) (ids->ne[0] * ids->ne[1]) * (double) as->ne[1] * (double) row_size(as->type, as->ne[0]));
+                    if (as->type == GGML_TYPE_BF16 || as->type == GGML_TYPE_F32) mmv_id_f(a, s.st);
+                    else if (as->type == GGML_TYPE_MXFP4) mmv_id_mxfp4(a, s.st);
                     else if (as->type == GGML_TYPE_Q4_K || as->type == GGML_TYPE_Q5_K || as->type == GGML_TYPE_Q6_K) mmv_id_kquant(a, s.st);
                     else mmv_id_blocks(a, s.st);                          // the nine block forms of mmvq.hip
                     ++s.n_kernels;

@@ -32,7 +32,7 @@ struct byte_range { const char * lo; const char * hi; };
 static inline byte_range range_of(const ggml_tensor * t) { const char * p = (const char *) t->data; return { p, p + nbytes(t) }; }
 static inline bool overlap(byte_range a, byte_range b) { return a.lo < b.hi && b.lo < a.hi && a.lo != a.hi && b.lo != b.hi; }
 
-enum act_kind { ACT_NONE = 0, ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32, ACT_Q8KT, ACT_F16Q, ACT_Q81 };      // Q81: the Q8_0 image plus the per-block s = d * sum(qs) (Q4_1 / Q5_1 weights)      // F16Q: f16 rows of the Q8_K-quantised values (what the F16-image GEMMs of K-quant weights multiply with)      // Q8KT: the block-major Q8_K image of a whole ubatch (mmq_tile.hip), not a per-row format
+enum act_kind { ACT_NONE = 0, ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32, ACT_Q8KT, ACT_F16Q, ACT_Q81, ACT_BF16 };      // BF16: bf16 rows, zero-padded to 16 bytes (MUL_MAT_ID on BF16 experts: the reference's ggml_compute_fp32_to_bf16 of every column, mm_id_f.hip)      // Q81: the Q8_0 image plus the per-block s = d * sum(qs) (Q4_1 / Q5_1 weights)      // F16Q: f16 rows of the Q8_K-quantised values (what the F16-image GEMMs of K-quant weights multiply with)      // Q8KT: the block-major Q8_K image of a whole ubatch (mmq_tile.hip), not a per-row format
 // block formats whose only kernels of their own are the integer mat-vecs of mmvq.hip (up to 8 columns: Q4_1 / Q5_1 on Q8_1 images, Q2_K / Q3_K on
 // Q8_K images): from 9 columns on every MUL_MAT runs on the F16 image of the weights (resident for model tensors, shadow.hpp, built by the first
 // GEMM; else de-quantised into scratch per call) with f16-rounded activations.  Q2_K / Q3_K share the Q8_K image with the K-quants, but none of
@@ -45,7 +45,7 @@ static inline size_t act_image_bytes(act_kind k, int64_t K) {
         case ACT_Q8K: return q8k_image_bytes(K);
         case ACT_Q80: return q80_image_bytes(K);
         case ACT_Q81: return q81_image_bytes(K);
-        case ACT_F16: case ACT_F16Q: return ((size_t) K * 2 + 15) & ~(size_t) 15;
+        case ACT_F16: case ACT_F16Q: case ACT_BF16: return ((size_t) K * 2 + 15) & ~(size_t) 15;
         default: return 0;
     }
 }
@@ -206,8 +206,10 @@ struct mm_route {
 mm_route route_mul_mat(const ggml_tensor * n);
 // ... and a MUL_MAT_ID node: admitted or not (supports_op), the image of b's columns its path reads (both paths of a K-quant node read ACT_Q8K, both of an MXFP4 node
 // ACT_Q80, a block-form node the image of its dense mat-vec) and the path: the per-pair mat-vec, or from MMQ_ID_MIN_TOKENS (K-quants) / mmq_id_mxfp4_min_tokens() (MXFP4) /
-// mmq_id_blocks_min_tokens() (Q8_0, Q4_0, Q5_0, IQ4_NL) tokens on the expert-grouped int8-MFMA kernel of the type (scratch sizing, the executor's MUL_MAT_ID case)
-enum mm_id_path { MM_ID_MMV, MM_ID_MMQ };
+// mmq_id_blocks_min_tokens() (Q8_0, Q4_0, Q5_0, IQ4_NL) tokens on the expert-grouped int8-MFMA kernel of the type (scratch sizing, the executor's MUL_MAT_ID case).
+// BF16 experts read ACT_BF16 on both paths (MM_ID_BF16: the grouped bf16-MFMA kernel, from mm_id_bf16_min_tokens() tokens on); F32 experts read b's f32 columns where they
+// lie (ACT_F32: no image) and stay per-pair at every token count
+enum mm_id_path { MM_ID_MMV, MM_ID_MMQ, MM_ID_BF16 };
 struct mm_id_route { bool ok; act_kind act; mm_id_path path; };
 mm_id_route route_mul_mat_id(const ggml_tensor * n);
 // the token count from which K-quant experts take the grouped kernel.  Above 33: up to there one mmv_id launch per node is what the per-pair tests count.
@@ -224,6 +226,12 @@ int64_t mmq_id_mxfp4_min_tokens();
 static const int64_t MMQ_ID_BLOCKS_MIN_TOKENS = 65;
 static_assert(MMQ_ID_BLOCKS_MIN_TOKENS > 64, "the per-pair block-form mat-vec keeps every token count up to 64");
 int64_t mmq_id_blocks_min_tokens();
+// ... and BF16 experts theirs (mm_id_f.hip k_mm_id_16).  The value started at 65, inherited from MMQ_ID_BLOCKS_MIN_TOKENS; 32 is the measured one: at the Qwen3-30B-A3B
+// expert shapes (128 experts, 8 used) the grouped kernel loses at 8 and 16 tokens (0.71 - 0.94 x), wins at 32 (1.15 x down, 1.23 x gate / up; run-to-run spread <= 3.1 %)
+// and at every larger count (1.9 - 2.0 x at 64, 9 x at 512) -- tools/moe_mmq_bench.py --legs bf16, profiles/moe_bf16_crossover.txt.  No count between 16 and 32 was
+// measured.  MI355X_MM_ID_BF16_MIN_TOKENS (read once, floor 1) moves it: mm_id_bf16_min_tokens()
+static const int64_t MM_ID_BF16_MIN_TOKENS = 32;
+int64_t mm_id_bf16_min_tokens();
 void mmq_id_set_mode(int m);                            // option "mmq_id": 0 = every node on the per-pair kernel
 // one row per admitted weight type (null: none; BF16 has a path of its own): the image its mat-vec kernels read, their launcher (up to 8 columns) and profile class
 struct mmv_row { int type; act_kind act; void (*launch)(const mmv_args &, hipStream_t); const char * cls; };

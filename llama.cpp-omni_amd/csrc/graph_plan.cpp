@@ -376,9 +376,32 @@ mm_route route_mul_mat(const ggml_tensor * n) {
 //              for the rest);
 //   MM_ID_MMQ  Q8_0 / Q4_0 / Q5_0 / IQ4_NL (a 32-weight block against the Q8_0 image, no min term) from mmq_id_blocks_min_tokens() tokens on: the grouping, then one int8
 //              MFMA per block (mmq_id.hip, the MXFP4 body with another block decoder).  Q4_1 / Q5_1 / Q2_K / Q3_K / IQ4_XS experts stay per-pair at every token count.
-// F16 / F32 / BF16 experts have no kernel with the id indirection: refused, they stay on the CPU.  So are TQ1_0 / TQ2_0 experts (no id form of their kernels yet).
+// Unquantised experts (mm_id_f.hip):
+//   MM_ID_MMV  BF16 (ACT_BF16: every column of b rounded to bf16, as the reference's vec_dot_type conversion) and F32 (b's f32 columns in place, no image): the per-pair
+//              mat-vec k_mmv_id_f, any K >= 1 whose column fits 152 KiB of LDS, rows and experts element-aligned (16-byte loads where base, strides and K allow, chosen
+//              at the launch).  F32 experts take it at every token count.
+//   MM_ID_BF16 BF16 experts from mm_id_bf16_min_tokens() tokens on, K % 16 == 0, base / row stride / expert stride 16-byte aligned: the grouping, then
+//              v_mfma_f32_32x32x16_bf16 per (expert, 32 rows, <= 32 columns) on the weight rows and the same images (k_mm_id_16).  Option "mmq_id" = 0 keeps this
+//              family per-pair as well.
+// F16 experts have no kernel with the id indirection yet (one more element decoder and one route line): refused, they stay on the CPU.  So are TQ1_0 / TQ2_0 experts
+// (no id form of their kernels yet).
 static int g_mmq_id = -1;                                     // option "mmq_id": -1 = MI355X_MMQ_ID decides (default on), 0 off (the cross-check switch), 1 on
 void mmq_id_set_mode(int m) { g_mmq_id = m; }
+static bool mmq_id_on() {
+    static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
+    return (g_mmq_id >= 0 ? g_mmq_id : env) != 0;
+}
+int64_t mm_id_bf16_min_tokens() {
+    static const int64_t v = [] { const char * e = getenv("MI355X_MM_ID_BF16_MIN_TOKENS"); const int64_t n = e ? atoll(e) : MM_ID_BF16_MIN_TOKENS; return n < 1 ? (int64_t) 1 : n; }();
+    return v;
+}
+// a BF16 node takes the grouped bf16-MFMA kernel: the option, enough tokens, whole MFMA steps, 16-byte loads for every expert's rows, a pair list and an expert
+// histogram of bounded size, the kernel's LDS (the fold area and the slice's dst offsets: a constant).  Anything else stays on the per-pair kernel
+static bool mm_id_bf16_grouped(const ggml_tensor * as, const ggml_tensor * ids) {
+    if (as->type != GGML_TYPE_BF16 || !mmq_id_on() || ids->ne[1] < mm_id_bf16_min_tokens()) return false;
+    if (as->ne[0] % 16 != 0 || (((uintptr_t) as->data | as->nb[1] | as->nb[2]) & 15) != 0) return false;
+    return ids->ne[0] * ids->ne[1] <= MMQ_ID_MAX_PAIRS && as->ne[2] <= MMQ_ID_MAX_EXPERTS && mm_id_bf16_lds_bytes() <= MMQ_ID_LDS_MAX;
+}
 int64_t mmq_id_mxfp4_min_tokens() {
     static const int64_t v = [] { const char * e = getenv("MI355X_MMQ_ID_MXFP4_MIN_TOKENS"); const int64_t n = e ? atoll(e) : MMQ_ID_MXFP4_MIN_TOKENS; return n < 65 ? (int64_t) 65 : n; }();
     return v;
@@ -391,9 +414,8 @@ int64_t mmq_id_blocks_min_tokens() {
 // columns' block scales: K up to ~70 k for K-quants, ~9 k for the 32-weight blocks) and, for K-quants, the MFMA body's vector-load alignment for expert 0 and (through
 // nb[2]) every other expert
 static bool mm_id_grouped(const ggml_tensor * as, const ggml_tensor * ids) {
-    static const int env = getenv("MI355X_MMQ_ID") ? atoi(getenv("MI355X_MMQ_ID")) : 1;
     const int fam = mmq_id_family(as->type);
-    if (fam < 0 || !(g_mmq_id >= 0 ? g_mmq_id : env)) return false;
+    if (fam < 0 || !mmq_id_on()) return false;
     const int64_t K = as->ne[0], min_tokens = fam == MMQ_ID_KQUANT ? MMQ_ID_MIN_TOKENS : fam == MMQ_ID_MXFP4 ? mmq_id_mxfp4_min_tokens() : mmq_id_blocks_min_tokens();
     if (ids->ne[1] < min_tokens || ids->ne[0] * ids->ne[1] > MMQ_ID_MAX_PAIRS || as->ne[2] > MMQ_ID_MAX_EXPERTS || mmq_id_lds_bytes(as->type, K) > MMQ_ID_LDS_MAX) return false;
     return fam != MMQ_ID_KQUANT || (mmq_ok(as->type, K, as->data, as->nb[1]) && (as->ne[2] == 1 || mmq_ok(as->type, K, (const char *) as->data + as->nb[2], as->nb[1])));
@@ -405,7 +427,8 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     const int t = as->type;
     const bool blocks = t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_IQ4_NL ||
                         t == GGML_TYPE_IQ4_XS || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K;
-    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K && t != GGML_TYPE_MXFP4 && !blocks) return r;
+    const bool plain = t == GGML_TYPE_BF16 || t == GGML_TYPE_F32;
+    if (t != GGML_TYPE_Q4_K && t != GGML_TYPE_Q5_K && t != GGML_TYPE_Q6_K && t != GGML_TYPE_MXFP4 && !blocks && !plain) return r;
     if (b->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32 || ids->type != GGML_TYPE_I32) return r;
     if (as->nb[0] != type_size(t) || b->nb[0] != 4 || n->nb[0] != 4 || ids->nb[0] % 4 != 0 || ids->nb[1] % 4 != 0 || b->nb[1] % 4 != 0) return r;
     if (as->ne[3] != 1 || b->ne[3] != 1 || ids->ne[2] != 1 || ids->ne[3] != 1 || n->ne[3] != 1) return r;                 // the asserts of ggml_mul_mat_id (ggml.c:3088-3096)
@@ -413,6 +436,15 @@ mm_id_route route_mul_mat_id(const ggml_tensor * n) {
     if (n->ne[0] != as->ne[1] || n->ne[1] != ids->ne[0] || n->ne[2] != b->ne[2]) return r;
     if (ids->ne[0] > 65535 || b->ne[2] > 65535 || as->ne[2] > INT32_MAX || as->ne[1] > INT32_MAX) return r;                // grid y / z
     const int64_t K = as->ne[0];
+    if (plain) {                                                                                                          // types, shapes and strides only: no ->data in what is ADMITTED
+        const size_t es = type_size(t);
+        if (K < 1 || K > INT32_MAX || (((size_t) K * es + 15) & ~(size_t) 15) > (size_t) 152 * 1024) return r;            // one column (bf16 image / f32) in LDS
+        if (as->nb[1] < (size_t) K * es || as->nb[1] % es != 0 || as->nb[2] % es != 0) return r;                          // rows and experts element-aligned
+        if (t == GGML_TYPE_F32 && b->nb[2] % 4 != 0) return r;                                                            // (b is read in place)
+        r.ok = true; r.act = t == GGML_TYPE_BF16 ? ACT_BF16 : ACT_F32;
+        if (mm_id_bf16_grouped(as, ids)) r.path = MM_ID_BF16;
+        return r;
+    }
     if (t == GGML_TYPE_MXFP4) {
         if (K < 32 || K % 32 != 0 || K > INT32_MAX || q80_image_bytes(K) > (size_t) 152 * 1024) return r;                 // one column's Q8_0 image in LDS
         if (as->nb[1] < row_size(t, K)) return r;
@@ -468,12 +500,12 @@ size_t graph_act_scratch_need(const ggml_cgraph * g) {
     }
     return need;
 }
-// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip; every family alike): one grouping per node, the largest node's
+// the grouped MUL_MAT_ID's pair list, tile table and tile count (mmq_id.hip; every family alike, the bf16-MFMA kernel of mm_id_f.hip too): one grouping per node, the largest node's
 size_t graph_moe_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;
     for (int i = 0; i < g->n_nodes; ++i) {
         const ggml_tensor * n = g->nodes[i];
-        if (n->op != GGML_OP_MUL_MAT_ID || is_empty(n) || route_mul_mat_id(n).path != MM_ID_MMQ) continue;
+        if (n->op != GGML_OP_MUL_MAT_ID || is_empty(n) || route_mul_mat_id(n).path == MM_ID_MMV) continue;
         const size_t b = moe_group_bytes(n->src[2]->ne[0] * n->src[2]->ne[1], n->src[0]->ne[2]);
         if (b > need) need = b;
     }

@@ -13,6 +13,9 @@ void quantize_q80_image(const float * x, size_t xs, void * img, int64_t K, int64
 void quantize_q81_image(const float * x, size_t xs, void * img, int64_t K, int64_t nrows, hipStream_t st);
 // f32 -> f16 (RNE) rows, dst row stride ys bytes
 void convert_f32_f16_rows(const float * x, size_t xs, uint16_t * y, size_t ys, int64_t K, int64_t nrows, hipStream_t st);
+// f32 -> bf16 rows (ggml_compute_fp32_to_bf16: RNE, a NaN kept quiet), the BF16 weights' vec_dot_type conversion (mm_id_f.hip): row (i1, i2) at x + i1 * nb1 + i2 * nb2,
+// i1 fastest, one launch; dst rows dense at ys bytes (a multiple of 16), the bytes behind the K values ZERO
+void convert_f32_bf16_rows(const float * x, size_t nb1, size_t nb2, int64_t n1, int64_t n2, uint16_t * y, size_t ys, int64_t K, hipStream_t st);
 // f16 rows of the Q8_K-quantised values (d * q, what the reference's integer dot products multiply K-quant weights with): K % 256 == 0; in place for rows a launch left as f16
 void convert_f32_f16q_rows(const float * x, size_t xs, uint16_t * y, size_t ys, int64_t K, int64_t nrows, hipStream_t st);
 void requant_f16_rows_q8k(uint16_t * y, size_t ys, int64_t K, int64_t nrows, hipStream_t st);
@@ -93,6 +96,7 @@ struct mmv_id_args {
     int64_t      b_ne1;
     float *      dst; size_t dst_nb1, dst_nb2; // f32 [nrows, n_ids, n_tokens]
     int64_t      K, nrows;
+    size_t       b_nb1 = 0, b_nb2 = 0;         // F32 experts only (mmv_id_f): act = b's f32 columns where they lie, column (i1, t) at i1 * b_nb1 + t * b_nb2
 };
 void mmv_id_kquant(const mmv_id_args & a, hipStream_t st);
 long mmv_id_launches();
@@ -105,6 +109,11 @@ long mmv_id_mxfp4_launches();
 // row stride, expert stride and base 4-byte aligned for Q4_1 / Q5_1 / Q2_K, 2-byte for the rest.  Counted apart (stat "mmv_id_blocks_launches").
 void mmv_id_blocks(const mmv_id_args & a, hipStream_t st);
 long mmv_id_blocks_launches();
+// the same on unquantised experts (mm_id_f.hip k_mmv_id_f): type = BF16 (act = the bf16 images of convert_f32_bf16_rows, ((2 K + 15) & ~15) bytes each; products of
+// bf16 values, f32 sums) or F32 (act = b's data, b_nb1 / b_nb2; no rounding).  Any K >= 1 whose column fits 152 KiB of LDS; rows and experts element-aligned -- 16-byte
+// loads where base, strides and K allow, element-wise otherwise.  Counted apart (stat "mmv_id_f_launches").
+void mmv_id_f(const mmv_id_args & a, hipStream_t st);
+long mmv_id_f_launches();
 
 // ---- batch-1 decode form (mmv1.hip): ONE activation column, Q4_K / Q6_K, K a multiple of 256 up to 16384 (whole steps of 4096 at the Qwen3-8B widths, TAIL instances otherwise).  The launch takes the f32
 // activation row itself -- x, or rms_norm(x) * norm_w (the RMS_NORM + MUL nodes in front of src1) -- and every workgroup builds the Q8_K
@@ -168,6 +177,11 @@ struct moe_tile { int expert, first, ncols; };          // one non-empty (expert
 struct moe_group_out { const int * count; const moe_tile * tiles; const int * list; };
 int64_t moe_tile_bound(int64_t n_pairs, int64_t n_expert);      // the host-side bound on the tile count: the matrix kernels' grid y
 moe_group_out moe_group_launch(const mmv_id_args & m, void * scratch, hipStream_t st);
+// ... and BF16 experts against many tokens on the bf16 matrix cores (mm_id_f.hip k_mm_id_16): the same grouping, then v_mfma_f32_32x32x16_bf16 per (expert, 32-row
+// tile, <= 32-column slice) on the weight rows and the bf16 images.  K % 16 == 0; base, row stride and expert stride 16-byte aligned; `m` as for mmv_id_f.
+size_t mm_id_bf16_lds_bytes();                          // the slice's dst offsets + the widest fold: <= MMQ_ID_LDS_MAX is the route's condition
+void   mm_id_bf16(const mmq_id_args & a, hipStream_t st);
+mmq_id_stat mm_id_bf16_stats();                         // read-only: the stats "mm_id_bf16_launches" / "mm_id_bf16_ks"
 // ---- Q4_K weights against a prefill ubatch (> 64 columns) on the int8 matrix cores, tiled (mmq_tile.hip): up to 3 matrices sharing the block-major
 // Q8_K image of the activations (quantize_q8k_tile_image); `resid`: dst = W.x + resid (single matrix, un-split); split-K slabs / deferred reductions as gemm_f16_multi
 struct mmqt_mat { const void * W; size_t w_rs; float * dst; size_t dst_cs; int64_t M; const float * resid = nullptr; size_t resid_cs = 0; };

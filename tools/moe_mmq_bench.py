@@ -17,7 +17,11 @@ MI355X_MMQ_ID_NT4=1 in the environment keeps every tile of the grouped kernel on
 DeepSeek-V2-Lite down shape (64 experts, 6 used, K 1408, M 2048); --types picks among the four.  MI355X_MMQ_ID_BLOCKS_MIN_TOKENS=65 in the environment puts every token
 count from 65 on the grouped path (the crossover measurement behind MMQ_ID_BLOCKS_MIN_TOKENS, profiles/moe_blocks_crossover.txt).
 
-usage: python tools/moe_mmq_bench.py [--reps 3] [--rounds 3] [--tokens 64,128,512,2048] [--legs kquant|blocks] [--types q8_0,q4_0,q5_0,iq4_nl]
+--legs bf16: BF16 experts at the Qwen3-30B-A3B shapes (gate / up 768 x 2048, down 2048 x 768), the grouped bf16-MFMA kernel (mm_id_f.hip k_mm_id_16) against the per-pair
+mat-vec (k_mmv_id_f) at 8 / 16 / 32 / 64 / 128 / 512 tokens: the crossover measurement behind MM_ID_BF16_MIN_TOKENS.  The leg sets MI355X_MM_ID_BF16_MIN_TOKENS=1 (unless
+the environment says otherwise) so that every token count reaches the grouped kernel with mmq_id = 1.
+
+usage: python tools/moe_mmq_bench.py [--reps 3] [--rounds 3] [--tokens 64,128,512,2048] [--legs kquant|blocks|bf16] [--types q8_0,q4_0,q5_0,iq4_nl]
 """
 import argparse
 import os
@@ -28,10 +32,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import load_pkg  # noqa: E402
 
-Q4_K, Q6_K, F32, I32 = 12, 14, 0, 26
+Q4_K, Q6_K, F32, I32, BF16 = 12, 14, 0, 26, 30
 BLOCKS = {"q8_0": 8, "q4_0": 2, "q5_0": 6, "iq4_nl": 20}
 E, F = 2048, 768
 KQ_STATS, BL_STATS = ("mmq_id_launches", "mmv_id_launches"), ("mmq_id_blocks_launches", "mmv_id_blocks_launches")      # (grouped, per-pair) launch counters
+BF_STATS = ("mm_id_bf16_launches", "mmv_id_f_launches")
 HBM = 8.0e12
 
 
@@ -53,11 +58,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--tokens", default="64,128,512,2048")
+    ap.add_argument("--tokens", default=None)
     ap.add_argument("--min-mib", type=int, default=768)
-    ap.add_argument("--legs", default="kquant", choices=["kquant", "blocks"])
+    ap.add_argument("--legs", default="kquant", choices=["kquant", "blocks", "bf16"])
     ap.add_argument("--types", default="q8_0,q4_0,q5_0,iq4_nl")
     args = ap.parse_args()
+    tokens = args.tokens or ("8,16,32,64,128,512" if args.legs == "bf16" else "64,128,512,2048")
+    if args.legs == "bf16":
+        os.environ.setdefault("MI355X_MM_ID_BF16_MIN_TOKENS", "1")   # (read once, at the first MUL_MAT_ID the library routes)
     pkg = load_pkg()
     from llama_cpp_omni_amd import qwen3
     from llama_cpp_omni_amd.ggml import Context, row_size
@@ -70,13 +78,19 @@ def main():
         legs = []
         for t in args.types.split(","):
             legs += [(f"qwen3-30b-a3b gate/up {t}", BLOCKS[t], E, F, True, 128, 8, BL_STATS), (f"deepseek-v2-lite down {t}", BLOCKS[t], 1408, 2048, False, 64, 6, BL_STATS)]
+    if args.legs == "bf16":
+        legs = [("gate/up BF16", BF16, E, F, True, 128, 8, BF_STATS), ("down    BF16", BF16, F, E, False, 128, 8, BF_STATS)]
+    unit = "bf16 TFLOP/s" if args.legs == "bf16" else "int8 TOP/s"
     for name, ty, K, M, bcast, X, XU, stats in legs:
         tensor_bytes = X * M * row_size(ty, K)
         n_tensors = ((args.min_mib << 20) + tensor_bytes - 1) // tensor_bytes
         n_nodes = max(8, n_tensors)
-        host = qwen3.random_blocks(rng, ty, 1024, K)
+        if ty == BF16:                                                # (random_blocks has no BF16 form: the upper halves of f32 normals at std 0.02)
+            host = ((rng.standard_normal((1024, K)) * 0.02).astype(np.float32).view(np.uint32) >> 16).astype(np.uint16)
+        else:
+            host = qwen3.random_blocks(rng, ty, 1024, K)
         full = np.tile(host, (M * X // 1024, 1))
-        for T in [int(t) for t in args.tokens.split(",")]:
+        for T in [int(t) for t in tokens.split(",")]:
             c = Context(be)
             b = c.new_tensor(F32, K, 1 if bcast else XU, T)
             ws = [c.new_tensor(ty, K, M, X) for _ in range(n_tensors)]
@@ -108,7 +122,7 @@ def main():
             g, p = min(us[1]), min(us[0])
             print(f"{name} tokens={T:5d} pairs={XU * T:6d} experts touched {touched:6.1f}: grouped {g:9.2f} us/node (rounds " + " ".join(f"{v:.2f}" for v in us[1]) +
                   f"; spread {100 * (max(us[1]) - g) / g:.1f}%)  per-pair {p:9.2f} us/node (rounds " + " ".join(f"{v:.2f}" for v in us[0]) + f"; spread {100 * (max(us[0]) - p) / p:.1f}%)  "
-                  f"per-pair / grouped {p / g:6.2f}  floor {floor:6.2f} us (grouped = {g / floor:5.2f} x)  int8 {ops / g / 1e6:7.1f} TOP/s", flush=True)
+                  f"per-pair / grouped {p / g:6.2f}  floor {floor:6.2f} us (grouped = {g / floor:5.2f} x)  {unit.rsplit(' ', 1)[0]} {ops / g / 1e6:7.1f} {unit.rsplit(' ', 1)[1]}", flush=True)
 
 
 if __name__ == "__main__":
