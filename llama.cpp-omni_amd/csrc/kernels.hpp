@@ -387,6 +387,9 @@ void   fattn_set_gqa(bool on);   // matrix-core decode kernel on (default) / off
 void   fattn_set_wide(int m);     // option "fattn_wide": the matrix-core kernel for head sizes 40 / 72 / 80 / 96 / 112 / 256, 192 / 128 and 576 / 512 (fattn_wide.hip): -1 default (on), 0 off (the generic kernel), 1 on
 long   fattn_wide_launches();
 bool   fattn_wide_takes(const fattn_args & a);    // that kernel will run (fa_wide_plan); fattn_scratch_bytes() is then its slices' workspace, 0 with one slice
+void   fattn_set_q(int m);        // option "fattn_q": the matrix-core kernel for head sizes 64 / 128 over a Q8_0 / Q4_0 cache (fattn_q.hip): -1 default (on), 0 off (the generic kernel), 1 on
+long   fattn_q_launches();
+bool   fattn_q_takes(const fattn_args & a);       // that kernel will run (fa_q_plan); fattn_scratch_bytes() is then its slices' workspace, 0 with one slice
 bool   fattn_uses_mma(const fattn_args & a);      // the matrix-core (prefill) kernel will run: out16 is honoured
 void   flash_attn_ext_f16(const fattn_args & a, hipStream_t st);
 

@@ -467,6 +467,44 @@ static wide_plan fa_wide_plan(const fattn_args & f) {
 }
 bool fattn_wide_takes(const fattn_args & f) { return fa_wide_plan(f).ok; }
 
+// Head size 64 / 128 over a Q8_0 / Q4_0 cache (K and V alike): k_fattn_q (fattn_q.hip).  The single place that decides whether that kernel takes a node and in how many
+// KV slices: consulted by the dispatch below, by fattn_scratch_bytes and through fattn_q_takes by the executor.  Everything it refuses -- ALiBi, a mask per head, other
+// head sizes, BF16 / F32 caches, odd strides -- stays on the generic kernel (fattn_any.hip) exactly as before.  Direct limit and slice rule: fa_wide_plan's.
+static int g_q_mode = -1;
+void fattn_set_q(int m) { g_q_mode = m; }
+struct q_plan { bool ok; int nsplit; };
+static q_plan fa_q_plan(const fattn_args & f) {
+    static const bool off = getenv("MI355X_FA_NO_Q") != nullptr;
+    q_plan p = { false, 1 };
+    if (g_q_mode == 0 || (g_q_mode < 0 && off)) return p;
+    if (f.kv_type != GGML_TYPE_Q8_0 && f.kv_type != GGML_TYPE_Q4_0) return p;
+    const int64_t D = f.q.ne[0];
+    if ((D != 64 && D != 128) || f.k.ne[0] != D || f.v.ne[0] != D) return p;
+    if (f.v_transposed || f.pre || f.img || f.out16 || f.max_bias != 0.0f) return p;
+    const int64_t nq = f.q.ne[1], nh = f.q.ne[2], nhkv = f.k.ne[2], nkv = f.k.ne[1], ns = f.q.ne[3];
+    if (nq < 1 || nh < 1 || nhkv < 1 || nkv < 1 || ns < 1 || nh % nhkv != 0 || f.v.ne[1] != nkv || f.v.ne[2] != nhkv) return p;
+    if (f.mask && (f.mask->ne[2] != 1 || f.mask->nb[0] != 2 || f.mask->ne[0] < nkv || f.mask->ne[1] < nq)) return p;      // (a per-head mask would need per-lane mask rows)
+    const int64_t ntile = (nkv + 31) / 32;
+    if (ntile > fattn_q_max_tiles() || nq * nh * ns > (int64_t) 1 << 30) return p;
+    // Q and the output rows go as f32x4: 16-byte rows and bases.  K / V rows are whole 34- / 18-byte blocks: 2-byte alignment is all the kernel's loads need
+    // (they stay inside a block), and all a view of such a cache has -- odd strides or an odd base are refused
+    auto al = [](const tdesc & t, size_t n) { return ((uintptr_t) t.p | t.nb[1] | t.nb[2] | t.nb[3]) % n == 0; };
+    const size_t row = (size_t) (D / 32) * (f.kv_type == GGML_TYPE_Q8_0 ? 34 : 18);
+    if (!al(f.q, 16) || !al(f.dst, 16) || f.q.nb[0] != 4 || f.dst.nb[0] != 4 || !al(f.k, 2) || !al(f.v, 2) || f.k.nb[1] < row || f.v.nb[1] < row) return p;
+    p.ok = true;
+    if (ntile > FA_WIDE_DIRECT_TILES) {
+        const int64_t gq = nh / nhkv;
+        const int64_t nct = gq >= 32 ? nq * ((gq + 31) / 32) : (nq + 32 / gq - 1) / (32 / gq);
+        const int64_t wgs = (nct + 3) / 4 * nhkv * ns;                                                // four column tiles per workgroup (fattn_q.hip)
+        int64_t s = 512 / wgs;
+        if (s > ntile / 4) s = ntile / 4;
+        if (s > 128) s = 128;
+        if (s >= 2) { const int64_t tps = (ntile + s - 1) / s; p.nsplit = (int) ((ntile + tps - 1) / tps); }     // (no empty slice)
+    }
+    return p;
+}
+bool fattn_q_takes(const fattn_args & f) { return fa_q_plan(f).ok; }
+
 template <int D, int R, int NW>
 static size_t fa_lds_bytes() { return (size_t) R * D * 4 + NW * 16 * R * 4 + NW * R * (D + 2) * 4; }
 
@@ -490,6 +528,8 @@ size_t fattn_map_bytes_host(int64_t nq, int64_t nkv) { return fattn_map_bytes(nq
 size_t fattn_scratch_bytes(const fattn_args & f) {
     if (const wide_plan wp = fa_wide_plan(f); wp.ok)                  // partial (O, M, S) rows of the slices: columns x slices x (DV + 2) floats
         return wp.nsplit > 1 ? (size_t) (f.q.ne[1] * f.q.ne[2] * f.q.ne[3]) * (size_t) wp.nsplit * (size_t) (f.v.ne[0] + 2) * 4 : 0;
+    if (const q_plan qp = fa_q_plan(f); qp.ok)                        // the same for the quantised-cache kernel
+        return qp.nsplit > 1 ? (size_t) (f.q.ne[1] * f.q.ne[2] * f.q.ne[3]) * (size_t) qp.nsplit * (size_t) (f.v.ne[0] + 2) * 4 : 0;
     if (!fa_use_mma(f)) {                                             // decode kernels: partial rows of the KV split
         fattn_args g = f; g.pre = nullptr;
         const gqa_plan gp = fa_gqa_plan(g);
@@ -599,6 +639,19 @@ void flash_attn_ext_f16(const fattn_args & f, hipStream_t st) {
                 default: fprintf(stderr, "[mi355x] flash_attn: no merge kernel for head size %d\n", DV); abort();
             }
 #undef FA_MERGE
+        }
+        return;
+    }
+    if (const q_plan qp = fa_q_plan(f); qp.ok) {                      // head 64 / 128 over a Q8_0 / Q4_0 cache: the matrix-core kernel of fattn_q.hip
+        const int D = (int) f.q.ne[0];
+        a.nsplit = 1; a.part = nullptr; a.tile_map = nullptr; a.map_nqb = 0;
+        if (qp.nsplit > 1 && f.scratch && f.scratch_bytes >= fattn_scratch_bytes(f)) { a.nsplit = qp.nsplit; a.part = (float *) f.scratch; }   // (no workspace: one slice, still correct)
+        flash_attn_ext_q(a, D, f.kv_type, st);
+        if (a.nsplit > 1) {
+            const int nblk = (int) ((a.nh * D + 255) / 256);
+            const dim3 grid((unsigned) (a.nq * a.ns * nblk));
+            if (D == 64) k_fattn_merge<64><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
+            else         k_fattn_merge<128><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
         }
         return;
     }

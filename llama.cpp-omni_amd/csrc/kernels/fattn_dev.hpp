@@ -53,5 +53,9 @@ void flash_attn_ext_any(const fa_dev & a, int Dk, int Dv, int kv_type, hipStream
 bool fattn_wide_dims(int64_t Dk, int64_t Dv);
 int  fattn_wide_max_tiles();                      // 32-row KV tiles a slice may hold (the kernel's live-tile bitmap)
 void flash_attn_ext_wide(const fa_dev & a, int Dk, int Dv, hipStream_t st);
+// head size 64 / 128 over a Q8_0 / Q4_0 cache on the matrix cores (fattn_q.hip): int8 MFMA scores against the query quantised in the kernel, f32 MFMA P . V; tiles,
+// slices and a.part as the wide kernel; fa_q_plan (fattn.hip) decides
+int  fattn_q_max_tiles();
+void flash_attn_ext_q(const fa_dev & a, int D, int kv_type, hipStream_t st);
 
 } // namespace mi
