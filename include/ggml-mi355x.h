@@ -60,6 +60,9 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * 0 sends those shapes to the generic one-wave-per-row kernel: the cross-check switch; process-wide, drops captured graphs),
  * "fattn_q" (-1 default (on) / 0 / 1: the matrix-core FLASH_ATTN_EXT kernel for head sizes 64 / 128 over a Q8_0 / Q4_0 KV cache, csrc/kernels/fattn_q.hip; 0 sends
  * those nodes to the generic one-wave-per-row kernel: the cross-check switch; process-wide, drops captured graphs; environment MI355X_FA_NO_Q is the default's off),
+ * "fattn_qx" (-1 default (on) / 0 / 1: the matrix-core FLASH_ATTN_EXT kernel for head sizes 64 / 128 over K in Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 and V in one of those or
+ * F16 -- mixed pairs and the Q4_1 / Q5_0 / Q5_1 caches, csrc/kernels/fattn_qx.hip; 0 sends those nodes to the generic kernel: the cross-check switch; process-wide, drops
+ * captured graphs; environment MI355X_FA_NO_QX is the default's off),
  * "prefill_q8k" (0 default / 1: the prefill GEMMs of K-quant weights take the Q8_K-QUANTISED activations -- the reference CPU backend's vec_dot_type
  * arithmetic, ggml-cpu.c:1245-1268 -- instead of plain f16 rows; process-wide), "mmq_tile" (0 default / 1: Q4_K weights x more than 64 columns on the int8
  * matrix cores from the blocks, csrc/kernels/mmq_tile.hip: the oracle's exact integer sums, slower than the F16-image GEMM; process-wide),
@@ -79,6 +82,7 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
 /* counters: "graph_replays", "graph_captures", "eager_graphs", "kernels_last_graph", "mmq_tile_launches",
  * "fattn_wide_launches" (launches of the head-size 256 / 576 attention kernel, csrc/kernels/fattn_wide.hip; the merge pass of a sliced node is not counted),
  * "fattn_q_launches" (launches of the quantised-cache attention kernel, csrc/kernels/fattn_q.hip; the merge pass of a sliced node is not counted),
+ * "fattn_qx_launches" (the same for the mixed-type / Q4_1 / Q5_0 / Q5_1 cache kernel, csrc/kernels/fattn_qx.hip),
  * "mmv_iq4nl_launches", "mmv_iq4xs_launches", "mmv_q41_launches", "mmv_q51_launches", "mmv_q2k_launches", "mmv_q3k_launches" (launches of the
  * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_tq1_launches", "mmv_tq2_launches" (the same for TQ1_0 / TQ2_0), "mmq_tq_launches" (launches of the
  * ternary int8-MFMA kernel, one per 2-D slice of a node) and "mmq_tq_ks" (not a counter: the K split of the most recent one, 0 before the first), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),

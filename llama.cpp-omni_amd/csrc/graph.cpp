@@ -387,6 +387,7 @@ int mi355x_set_option(struct ggml_backend * backend, const char * key, long valu
     if (!strcmp(key, "fattn_dma")) { mi::fattn_set_dma((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide)
     if (!strcmp(key, "fattn_wide")) { mi::fattn_set_wide((int) value); mi::drop_graph_execs(c); return 0; }    // (process-wide)
     if (!strcmp(key, "fattn_q")) { mi::fattn_set_q((int) value); mi::drop_graph_execs(c); return 0; }          // (process-wide)
+    if (!strcmp(key, "fattn_qx")) { mi::fattn_set_qx((int) value); mi::drop_graph_execs(c); return 0; }        // (process-wide)
     if (!strcmp(key, "f16_shadow")) { mi::shadow_set_enabled(value != 0); mi::drop_graph_execs(c); return 0; }
     if (!strcmp(key, "reset_stats")) { c->prof.clear(); c->stat_replays = c->stat_captures = c->stat_eager = 0; return 0; }
     return -1;
@@ -418,6 +419,7 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "fattn_dma_launches")) return (double) mi::fattn_dma_launches();
     if (!strcmp(key, "fattn_wide_launches")) return (double) mi::fattn_wide_launches();
     if (!strcmp(key, "fattn_q_launches"))   return (double) mi::fattn_q_launches();
+    if (!strcmp(key, "fattn_qx_launches"))  return (double) mi::fattn_qx_launches();
     if (!strcmp(key, "attn_vrows_launches")) return (double) mi::attn_vrows_launches();
     if (!strcmp(key, "fattn_gs_launches"))  return (double) mi::fattn_gs_launches();
     if (!strcmp(key, "fattn_gs_far_launches")) return (double) mi::fattn_gs_far_launches();

@@ -831,8 +831,8 @@ void exec_fattn(exec_state & s, int i) {
     ggml_tensor * n = g->nodes[i];
     fattn_args f; tdesc m;
     fill_fattn_args(n, f, m);
-    if ((n->src[0]->ne[0] != 64 && n->src[0]->ne[0] != 128) || n->src[2]->ne[0] != n->src[0]->ne[0] || n->src[1]->type != GGML_TYPE_F16) {      // other head sizes / cache types: the generic kernel, no fused stage
-        if ((fattn_wide_takes(f) || fattn_q_takes(f)) && fattn_scratch_bytes(f) > 0) {      // a head size of fattn_wide.hip, or a Q8_0 / Q4_0 cache on fattn_q.hip, over a deep cache: workspace of the KV slices, columns x slices x (DV + 2) floats (+ the merge launch)
+    if ((n->src[0]->ne[0] != 64 && n->src[0]->ne[0] != 128) || n->src[2]->ne[0] != n->src[0]->ne[0] || n->src[1]->type != GGML_TYPE_F16 || n->src[2]->type != GGML_TYPE_F16) {      // other head sizes / cache types: the generic kernel, no fused stage
+        if ((fattn_wide_takes(f) || fattn_q_takes(f) || fattn_qx_takes(f)) && fattn_scratch_bytes(f) > 0) {      // a head size of fattn_wide.hip, or a quantised cache on fattn_q.hip / fattn_qx.hip, over a deep cache: workspace of the KV slices, columns x slices x (DV + 2) floats (+ the merge launch)
             f.scratch = fa_scratch_take(s, FA_KV_SPLIT, n); f.scratch_bytes = s.c->fa_scratch_bytes;
             ++s.n_kernels;
         }

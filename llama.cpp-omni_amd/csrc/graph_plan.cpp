@@ -203,18 +203,20 @@ bool supports_op(const ggml_tensor * op) {
         }
         case GGML_OP_SET_ROWS:
             return s0 && s1 && s0->type == GGML_TYPE_F32 &&
-                   (op->type == GGML_TYPE_F16 || op->type == GGML_TYPE_F32 || op->type == GGML_TYPE_BF16 || ((op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q4_0) && s0->ne[0] % 32 == 0)) &&
+                   (op->type == GGML_TYPE_F16 || op->type == GGML_TYPE_F32 || op->type == GGML_TYPE_BF16 || ((op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q4_0 || op->type == GGML_TYPE_Q4_1 || op->type == GGML_TYPE_Q5_0 || op->type == GGML_TYPE_Q5_1) && s0->ne[0] % 32 == 0)) &&
                    (s1->type == GGML_TYPE_I64 || s1->type == GGML_TYPE_I32) && s0->nb[0] == 4 && op->nb[0] == type_size(op->type);
         case GGML_OP_FLASH_ATTN_EXT: {
             const ggml_tensor * q = s0, * k = s1, * v = op->src[2], * m = op->src[3];
             if (!q || !k || !v) return false;
-            if (q->type != GGML_TYPE_F32 || k->type != v->type || op->type != GGML_TYPE_F32) return false;
-            if (k->type != GGML_TYPE_F16 && k->type != GGML_TYPE_F32 && k->type != GGML_TYPE_BF16 && k->type != GGML_TYPE_Q8_0 && k->type != GGML_TYPE_Q4_0) return false;
+            if (q->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32) return false;
+            // K and V each one of F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 in any combination (-ctk / -ctv); BF16 and F32 caches same-type only.  IQ4_NL caches: CPU (their store needs the reference's scale search)
+            auto mixable = [](int t) { return t == GGML_TYPE_F16 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1; };
+            if (!(mixable(k->type) && mixable(v->type)) && !(k->type == v->type && (k->type == GGML_TYPE_F32 || k->type == GGML_TYPE_BF16))) return false;
             if (q->ne[0] != k->ne[0]) return false;
-            // the MFMA / streaming / one-token kernels (F16 cache, head 64 / 128); anything else -- other head sizes, a quantised / BF16 / F32 cache -- fattn_wide.hip where fa_wide_plan takes it, fattn_q.hip where fa_q_plan does (head 64 / 128 over Q8_0 / Q4_0), else fattn_any.hip
-            const bool special = k->type == GGML_TYPE_F16 && (q->ne[0] == 64 || q->ne[0] == 128) && v->ne[0] == q->ne[0];
+            // the MFMA / streaming / one-token kernels (F16 cache, head 64 / 128); anything else -- other head sizes, a quantised / BF16 / F32 cache -- fattn_wide.hip where fa_wide_plan takes it, fattn_q.hip where fa_q_plan does (head 64 / 128 over Q8_0 / Q4_0), fattn_qx.hip where fa_qx_plan does (head 64 / 128 over mixed types, Q4_1 / Q5_0 / Q5_1), else fattn_any.hip
+            const bool special = k->type == GGML_TYPE_F16 && v->type == GGML_TYPE_F16 && (q->ne[0] == 64 || q->ne[0] == 128) && v->ne[0] == q->ne[0];
             if (!special && (q->ne[0] > 576 || v->ne[0] > 576)) return false;
-            if ((k->type == GGML_TYPE_Q8_0 || k->type == GGML_TYPE_Q4_0) && (k->ne[0] % 32 != 0 || v->ne[0] % 32 != 0)) return false;
+            if ((k->type != GGML_TYPE_F16 && mixable(k->type) && k->ne[0] % 32 != 0) || (v->type != GGML_TYPE_F16 && mixable(v->type) && v->ne[0] % 32 != 0)) return false;
             if (q->nb[0] != 4 || k->nb[0] != type_size(k->type) || v->nb[0] != type_size(v->type)) return false;
             if (special && (k->nb[1] % 16 != 0 || v->nb[1] % 16 != 0 || k->nb[2] % 16 != 0 || v->nb[2] % 16 != 0)) return false;
             if (m && (m->type != GGML_TYPE_F16 || m->nb[0] != 2)) return false;
@@ -527,7 +529,7 @@ void fill_fattn_args(const ggml_tensor * n, fattn_args & f, tdesc & m) {
     f.mask = n->src[3] ? &m : nullptr;
     f.sinks = n->src[4] ? (const float *) n->src[4]->data : nullptr;
     f.scale = op_param_f32(n, 0); f.max_bias = op_param_f32(n, 1); f.logit_softcap = op_param_f32(n, 2);
-    f.scratch = nullptr; f.scratch_bytes = 0; f.kv_type = n->src[1]->type;
+    f.scratch = nullptr; f.scratch_bytes = 0; f.kv_type = n->src[1]->type; f.v_type = n->src[2]->type;
 }
 size_t graph_fa_scratch_need(const ggml_cgraph * g) {
     size_t need = 0;

@@ -329,7 +329,8 @@ struct fattn_pre {
 // FLASH_ATTN_EXT (ops.cpp:7912-8148): q f32 [D, nq, nh, ns], k/v f16 [D, nkv, nhkv, ns], mask f16 [nkv, >=nq, 1|nh?, ns]
 struct fattn_args {
     tdesc q, k, v, dst;
-    int kv_type = 1;         // GGML type of K and V (F16 = 1: every specialised kernel; F32 / BF16 / Q8_0 / Q4_0: fattn_any.hip)
+    int kv_type = 1;         // GGML type of K (F16 = 1: every specialised kernel; F32 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1: fattn_q.hip, fattn_qx.hip, fattn_any.hip)
+    int v_type = 1;          // GGML type of V: kv_type, or -- K and V each one of F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 -- another one (fattn_qx.hip, fattn_any.hip)
     const tdesc * mask;      // may be null
     const float * sinks;     // may be null
     float scale, max_bias, logit_softcap;
@@ -390,6 +391,9 @@ bool   fattn_wide_takes(const fattn_args & a);    // that kernel will run (fa_wi
 void   fattn_set_q(int m);        // option "fattn_q": the matrix-core kernel for head sizes 64 / 128 over a Q8_0 / Q4_0 cache (fattn_q.hip): -1 default (on), 0 off (the generic kernel), 1 on
 long   fattn_q_launches();
 bool   fattn_q_takes(const fattn_args & a);       // that kernel will run (fa_q_plan); fattn_scratch_bytes() is then its slices' workspace, 0 with one slice
+void   fattn_set_qx(int m);       // option "fattn_qx": the matrix-core kernel for head sizes 64 / 128 over mixed K / V cache types and Q4_1 / Q5_0 / Q5_1 caches (fattn_qx.hip): -1 default (on), 0 off (the generic kernel), 1 on
+long   fattn_qx_launches();
+bool   fattn_qx_takes(const fattn_args & a);      // that kernel will run (fa_qx_plan); fattn_scratch_bytes() is then its slices' workspace, 0 with one slice
 bool   fattn_uses_mma(const fattn_args & a);      // the matrix-core (prefill) kernel will run: out16 is honoured
 void   flash_attn_ext_f16(const fattn_args & a, hipStream_t st);
 

@@ -1354,7 +1354,10 @@ __global__ void __launch_bounds__(256) k_set_rows_1elem(const char * __restrict_
 // SET_ROWS into a quantised / BF16 table (a KV cache kept as Q8_0 / Q4_0 / BF16: llama_kv_cache::cpy_k / cpy_v with -ctk / -ctv): the row goes
 // through the type's from_float like ggml_compute_forward_set_rows_f32 does -- quantize_row_q8_0 as the x86 build compiles it (d = amax / 127 stored
 // as f16, id = 127 / amax, round-half-even), quantize_row_q4_0_ref (ggml-quants.c: the FIRST value of largest magnitude decides d = max / -8,
-// q = min(15, (int8) (x / d + 8.5))), ggml_compute_fp32_to_bf16.  One thread per 32-element block (per element for BF16).
+// q = min(15, (int8) (x / d + 8.5))), ggml_compute_fp32_to_bf16.  Q4_1 / Q5_0 / Q5_1 tables: quantize_row_q4_1_ref (ggml-quants.c:73-108: d = (max - min) / 15,
+// m = min, q = min(15, (int8) ((x - min) / d + 0.5))), quantize_row_q5_0_ref (:110-152: as Q4_0 with d = max / -16, q = min(31, (int8) (x / d + 16.5)), the fifth bits
+// in qh: element j at bit j) and quantize_row_q5_1_ref (:154-196: d = (max - min) / 31, q = (uint8) ((x - min) / d + 0.5)) -- the CPU backend's from_float of these
+// types is the _ref function itself (ggml-cpu.c type traits -> ggml-cpu/quants.c quantize_row_q4_1 / q5_0 / q5_1).  One thread per 32-element block (per element for BF16).
 template <int T, typename TI>
 __global__ void __launch_bounds__(256) k_set_rows_q(td4 s, td4 idx, td4 d, int64_t total) {
     const int64_t t = (int64_t) blockIdx.x * 256 + threadIdx.x;
@@ -1380,6 +1383,40 @@ __global__ void __launch_bounds__(256) k_set_rows_q(td4 s, td4 idx, td4 d, int64
         char * b = dr + ib * 34;
         *(uint16_t *) b = f2h(dd);
         for (int j = 0; j < 32; ++j) b[2 + j] = (char) (int8_t) (int) rintf(x[j] * id);
+    } else if (T == GGML_TYPE_Q4_1 || T == GGML_TYPE_Q5_1) {
+        constexpr bool Q5 = T == GGML_TYPE_Q5_1;
+        float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
+        for (int j = 0; j < 32; ++j) { const float v = x[j]; if (v < mn) mn = v; if (v > mx) mx = v; }
+        const float dd = (mx - mn) / (Q5 ? 31.0f : 15.0f), id = dd != 0.0f ? 1.0f / dd : 0.0f;
+        char * b = dr + ib * (Q5 ? 24 : 20);
+        *(uint16_t *) b = f2h(dd); *(uint16_t *) (b + 2) = f2h(mn);
+        uint32_t qh = 0u;
+        for (int j = 0; j < 16; ++j) {
+            const float x0 = (x[j] - mn) * id, x1 = (x[16 + j] - mn) * id;
+            if (Q5) {
+                const uint32_t q0 = (uint8_t) (x0 + 0.5f), q1 = (uint8_t) (x1 + 0.5f);
+                b[8 + j] = (char) ((q0 & 0x0Fu) | ((q1 & 0x0Fu) << 4));
+                qh |= ((q0 & 0x10u) >> 4) << j; qh |= ((q1 & 0x10u) >> 4) << (j + 16);
+            } else {
+                const int q0 = (int) (int8_t) (x0 + 0.5f), q1 = (int) (int8_t) (x1 + 0.5f);
+                b[4 + j] = (char) ((q0 < 15 ? q0 : 15) | ((q1 < 15 ? q1 : 15) << 4));
+            }
+        }
+        if (Q5) { *(uint16_t *) (b + 4) = (uint16_t) qh; *(uint16_t *) (b + 6) = (uint16_t) (qh >> 16); }
+    } else if (T == GGML_TYPE_Q5_0) {
+        float amax = 0.0f, mx = 0.0f;
+        for (int j = 0; j < 32; ++j) { const float v = x[j]; if (amax < fabsf(v)) { amax = fabsf(v); mx = v; } }
+        const float dd = mx / -16.0f, id = dd != 0.0f ? 1.0f / dd : 0.0f;
+        char * b = dr + ib * 22;
+        *(uint16_t *) b = amax == 0.0f ? (uint16_t) 0x8000u : f2h(dd);     // (an all-zero block: -0, as Q4_0 below)
+        uint32_t qh = 0u;
+        for (int j = 0; j < 16; ++j) {
+            const int i0 = (int) (int8_t) (x[j] * id + 16.5f), i1 = (int) (int8_t) (x[16 + j] * id + 16.5f);
+            const uint32_t q0 = (uint8_t) (i0 < 31 ? i0 : 31), q1 = (uint8_t) (i1 < 31 ? i1 : 31);
+            b[6 + j] = (char) ((q0 & 0x0Fu) | ((q1 & 0x0Fu) << 4));
+            qh |= ((q0 & 0x10u) >> 4) << j; qh |= ((q1 & 0x10u) >> 4) << (j + 16);
+        }
+        *(uint16_t *) (b + 2) = (uint16_t) qh; *(uint16_t *) (b + 4) = (uint16_t) (qh >> 16);
     } else {                                                             // Q4_0
         float amax = 0.0f, mx = 0.0f;
         for (int j = 0; j < 32; ++j) { const float v = x[j]; if (amax < fabsf(v)) { amax = fabsf(v); mx = v; } }
@@ -1395,14 +1432,15 @@ __global__ void __launch_bounds__(256) k_set_rows_q(td4 s, td4 idx, td4 d, int64
 
 void set_rows(const tdesc & src, const tdesc & idx, int idx_type, const tdesc & dst, int dst_type, hipStream_t st, int64_t period) {
     if (src.ne[0] * src.ne[1] * src.ne[2] * src.ne[3] == 0) return;
-    if (dst_type == GGML_TYPE_Q8_0 || dst_type == GGML_TYPE_Q4_0 || dst_type == GGML_TYPE_BF16) {
+    if (dst_type == GGML_TYPE_Q8_0 || dst_type == GGML_TYPE_Q4_0 || dst_type == GGML_TYPE_Q4_1 || dst_type == GGML_TYPE_Q5_0 || dst_type == GGML_TYPE_Q5_1 || dst_type == GGML_TYPE_BF16) {
         const int64_t per_row = dst_type == GGML_TYPE_BF16 ? src.ne[0] : src.ne[0] / 32;
         const int64_t total = per_row * src.ne[1] * src.ne[2] * src.ne[3];
         const dim3 grid((unsigned) ((total + 255) / 256));
         const td4 s = to_td4(src), i = to_td4(idx), d = to_td4(dst);
         const bool i64 = idx_type == GGML_TYPE_I64;
 #define SRQ(T) do { if (i64) k_set_rows_q<T, int64_t><<<grid, dim3(256), 0, st>>>(s, i, d, total); else k_set_rows_q<T, int32_t><<<grid, dim3(256), 0, st>>>(s, i, d, total); } while (0)
-        if (dst_type == GGML_TYPE_Q8_0) SRQ(GGML_TYPE_Q8_0); else if (dst_type == GGML_TYPE_Q4_0) SRQ(GGML_TYPE_Q4_0); else SRQ(GGML_TYPE_BF16);
+        if (dst_type == GGML_TYPE_Q8_0) SRQ(GGML_TYPE_Q8_0); else if (dst_type == GGML_TYPE_Q4_0) SRQ(GGML_TYPE_Q4_0); else if (dst_type == GGML_TYPE_Q4_1) SRQ(GGML_TYPE_Q4_1);
+        else if (dst_type == GGML_TYPE_Q5_0) SRQ(GGML_TYPE_Q5_0); else if (dst_type == GGML_TYPE_Q5_1) SRQ(GGML_TYPE_Q5_1); else SRQ(GGML_TYPE_BF16);
 #undef SRQ
         return;
     }

@@ -442,7 +442,7 @@ static wide_plan fa_wide_plan(const fattn_args & f) {
     static const bool off = getenv("MI355X_FA_NO_WIDE") != nullptr;
     wide_plan p = { false, 1, 4 };
     if (g_wide_mode == 0 || (g_wide_mode < 0 && off)) return p;
-    if (f.v_transposed || f.kv_type != GGML_TYPE_F16 || !fattn_wide_dims(f.q.ne[0], f.v.ne[0]) || f.k.ne[0] != f.q.ne[0]) return p;
+    if (f.v_transposed || f.kv_type != GGML_TYPE_F16 || f.v_type != GGML_TYPE_F16 || !fattn_wide_dims(f.q.ne[0], f.v.ne[0]) || f.k.ne[0] != f.q.ne[0]) return p;
     if (f.max_bias != 0.0f || f.pre || f.img || f.out16) return p;
     if (f.mask && f.mask->ne[2] != 1) return p;                       // (a per-head mask would need per-lane mask rows)
     const int64_t nq = f.q.ne[1], nh = f.q.ne[2], nhkv = f.k.ne[2], nkv = f.k.ne[1], ns = f.q.ne[3];
@@ -477,7 +477,7 @@ static q_plan fa_q_plan(const fattn_args & f) {
     static const bool off = getenv("MI355X_FA_NO_Q") != nullptr;
     q_plan p = { false, 1 };
     if (g_q_mode == 0 || (g_q_mode < 0 && off)) return p;
-    if (f.kv_type != GGML_TYPE_Q8_0 && f.kv_type != GGML_TYPE_Q4_0) return p;
+    if ((f.kv_type != GGML_TYPE_Q8_0 && f.kv_type != GGML_TYPE_Q4_0) || f.v_type != f.kv_type) return p;
     const int64_t D = f.q.ne[0];
     if ((D != 64 && D != 128) || f.k.ne[0] != D || f.v.ne[0] != D) return p;
     if (f.v_transposed || f.pre || f.img || f.out16 || f.max_bias != 0.0f) return p;
@@ -505,6 +505,53 @@ static q_plan fa_q_plan(const fattn_args & f) {
 }
 bool fattn_q_takes(const fattn_args & f) { return fa_q_plan(f).ok; }
 
+// Head size 64 / 128 over K in Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 and V in one of those or F16, but for the pairs fa_q_plan takes (Q8_0 / Q8_0, Q4_0 / Q4_0 -- whether or
+// not option "fattn_q" lets k_fattn_q run them): k_fattn_qx (fattn_qx.hip).  The single place that decides whether that kernel takes a node and in how many KV slices:
+// consulted by the dispatch below, by fattn_scratch_bytes and through fattn_qx_takes by the executor.  The refusals are fa_q_plan's -- transposed V, pre-stage, images,
+// out16, ALiBi, a mask per head, odd strides or base --, and F16 K over a quantised V: all of that stays on the generic kernel (fattn_any.hip).  Direct limit and slice
+// rule: fa_wide_plan's.
+static int g_qx_mode = -1;
+void fattn_set_qx(int m) { g_qx_mode = m; }
+static size_t fa_qx_row_bytes(int type, int64_t D) {
+    const size_t nb = (size_t) (D / 32);
+    switch (type) {
+        case GGML_TYPE_Q8_0: return nb * 34; case GGML_TYPE_Q4_0: return nb * 18; case GGML_TYPE_Q4_1: return nb * 20;
+        case GGML_TYPE_Q5_0: return nb * 22; case GGML_TYPE_Q5_1: return nb * 24; case GGML_TYPE_F16: return nb * 64;
+        default: return 0;
+    }
+}
+static q_plan fa_qx_plan(const fattn_args & f) {
+    static const bool off = getenv("MI355X_FA_NO_QX") != nullptr;
+    q_plan p = { false, 1 };
+    if (g_qx_mode == 0 || (g_qx_mode < 0 && off)) return p;
+    const int64_t D = f.q.ne[0];
+    if ((D != 64 && D != 128) || f.k.ne[0] != D || f.v.ne[0] != D) return p;
+    if (f.kv_type == GGML_TYPE_F16 || fa_qx_row_bytes(f.kv_type, D) == 0 || fa_qx_row_bytes(f.v_type, D) == 0) return p;
+    if (f.v_type == f.kv_type && (f.kv_type == GGML_TYPE_Q8_0 || f.kv_type == GGML_TYPE_Q4_0)) return p;               // k_fattn_q's pairs
+    if (f.v_transposed || f.pre || f.img || f.out16 || f.max_bias != 0.0f) return p;
+    const int64_t nq = f.q.ne[1], nh = f.q.ne[2], nhkv = f.k.ne[2], nkv = f.k.ne[1], ns = f.q.ne[3];
+    if (nq < 1 || nh < 1 || nhkv < 1 || nkv < 1 || ns < 1 || nh % nhkv != 0 || f.v.ne[1] != nkv || f.v.ne[2] != nhkv) return p;
+    if (f.mask && (f.mask->ne[2] != 1 || f.mask->nb[0] != 2 || f.mask->ne[0] < nkv || f.mask->ne[1] < nq)) return p;      // (a per-head mask would need per-lane mask rows)
+    const int64_t ntile = (nkv + 31) / 32;
+    if (ntile > fattn_qx_max_tiles() || nq * nh * ns > (int64_t) 1 << 30) return p;
+    // Q and the output rows go as f32x4: 16-byte rows and bases.  K / V rows are whole blocks (or halfs): 2-byte alignment is all the kernel's loads need
+    auto al = [](const tdesc & t, size_t n) { return ((uintptr_t) t.p | t.nb[1] | t.nb[2] | t.nb[3]) % n == 0; };
+    if (!al(f.q, 16) || !al(f.dst, 16) || f.q.nb[0] != 4 || f.dst.nb[0] != 4 || !al(f.k, 2) || !al(f.v, 2) ||
+        f.k.nb[1] < fa_qx_row_bytes(f.kv_type, D) || f.v.nb[1] < fa_qx_row_bytes(f.v_type, D)) return p;
+    p.ok = true;
+    if (ntile > FA_WIDE_DIRECT_TILES) {
+        const int64_t gq = nh / nhkv;
+        const int64_t nct = gq >= 32 ? nq * ((gq + 31) / 32) : (nq + 32 / gq - 1) / (32 / gq);
+        const int64_t wgs = (nct + 3) / 4 * nhkv * ns;                                                // four column tiles per workgroup (fattn_qx.hip)
+        int64_t s = 512 / wgs;
+        if (s > ntile / 4) s = ntile / 4;
+        if (s > 128) s = 128;
+        if (s >= 2) { const int64_t tps = (ntile + s - 1) / s; p.nsplit = (int) ((ntile + tps - 1) / tps); }     // (no empty slice)
+    }
+    return p;
+}
+bool fattn_qx_takes(const fattn_args & f) { return fa_qx_plan(f).ok; }
+
 template <int D, int R, int NW>
 static size_t fa_lds_bytes() { return (size_t) R * D * 4 + NW * 16 * R * 4 + NW * R * (D + 2) * 4; }
 
@@ -530,6 +577,8 @@ size_t fattn_scratch_bytes(const fattn_args & f) {
         return wp.nsplit > 1 ? (size_t) (f.q.ne[1] * f.q.ne[2] * f.q.ne[3]) * (size_t) wp.nsplit * (size_t) (f.v.ne[0] + 2) * 4 : 0;
     if (const q_plan qp = fa_q_plan(f); qp.ok)                        // the same for the quantised-cache kernel
         return qp.nsplit > 1 ? (size_t) (f.q.ne[1] * f.q.ne[2] * f.q.ne[3]) * (size_t) qp.nsplit * (size_t) (f.v.ne[0] + 2) * 4 : 0;
+    if (const q_plan xp = fa_qx_plan(f); xp.ok)                       // ... and for the mixed-type cache kernel
+        return xp.nsplit > 1 ? (size_t) (f.q.ne[1] * f.q.ne[2] * f.q.ne[3]) * (size_t) xp.nsplit * (size_t) (f.v.ne[0] + 2) * 4 : 0;
     if (!fa_use_mma(f)) {                                             // decode kernels: partial rows of the KV split
         fattn_args g = f; g.pre = nullptr;
         const gqa_plan gp = fa_gqa_plan(g);
@@ -655,10 +704,23 @@ void flash_attn_ext_f16(const fattn_args & f, hipStream_t st) {
         }
         return;
     }
-    if (!f.v_transposed && ((f.q.ne[0] != 64 && f.q.ne[0] != 128) || f.v.ne[0] != f.q.ne[0] || f.kv_type != GGML_TYPE_F16)) {     // other head sizes / cache types: the generic kernel (no pre-stage, no images)
+    if (const q_plan xp = fa_qx_plan(f); xp.ok) {                     // head 64 / 128 over mixed K / V cache types or Q4_1 / Q5_0 / Q5_1: the matrix-core kernel of fattn_qx.hip
+        const int D = (int) f.q.ne[0];
+        a.nsplit = 1; a.part = nullptr; a.tile_map = nullptr; a.map_nqb = 0;
+        if (xp.nsplit > 1 && f.scratch && f.scratch_bytes >= fattn_scratch_bytes(f)) { a.nsplit = xp.nsplit; a.part = (float *) f.scratch; }   // (no workspace: one slice, still correct)
+        flash_attn_ext_qx(a, D, f.kv_type, f.v_type, st);
+        if (a.nsplit > 1) {
+            const int nblk = (int) ((a.nh * D + 255) / 256);
+            const dim3 grid((unsigned) (a.nq * a.ns * nblk));
+            if (D == 64) k_fattn_merge<64><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
+            else         k_fattn_merge<128><<<grid, dim3(256), 0, st>>>(a.part, a.nsplit, a.nq, a.nh, nblk, a.sinks, a.dst, a.dnb1, a.dnb2, a.dnb3, nullptr, 0);
+        }
+        return;
+    }
+    if (!f.v_transposed && ((f.q.ne[0] != 64 && f.q.ne[0] != 128) || f.v.ne[0] != f.q.ne[0] || f.kv_type != GGML_TYPE_F16 || f.v_type != GGML_TYPE_F16)) {     // other head sizes / cache types: the generic kernel (no pre-stage, no images)
         if (f.pre || f.img || f.out16 || !fattn_any_ok(f.q.ne[0], f.v.ne[0])) { fprintf(stderr, "[mi355x] flash_attn: head size %d / %d with a fused stage\n", (int) f.q.ne[0], (int) f.v.ne[0]); abort(); }
         a.nsplit = 1; a.part = nullptr; a.tile_map = nullptr; a.map_nqb = 0;
-        flash_attn_ext_any(a, (int) f.q.ne[0], (int) f.v.ne[0], f.kv_type, st);
+        flash_attn_ext_any(a, (int) f.q.ne[0], (int) f.v.ne[0], f.kv_type, f.v_type, st);
         return;
     }
     if (f.pre && f.rope_tab && f.gs_parts && fattn_gs_ok(f)) {       // one token, <= 256 rows, the consumer folds the slices: one workgroup per (KV head, slice)

@@ -10,6 +10,11 @@
 // + slope * mask, masked cells skipped, online soft-max, sinks, 1 / S at the end.  The Q8_0 x Q8_0 / Q4_0 x Q8_0 block dots are integer sums times
 // d_k * d_q in the reference; here the same de-quantised factors are multiplied in f32 (differs by f32 rounding only).  V is accumulated in f32
 // (the reference's path for every V type but F16, where it accumulates in f16).
+// K and V of DIFFERENT types, and Q4_1 / Q5_0 / Q5_1 caches (K and V each one of F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1; what fa_qx_plan refuses, or option
+// "fattn_qx" = 0; head 64 / 128 otherwise runs on fattn_qx.hip): the instances T = FA_ANY_MIXED read K and V through separate run-time readers.  q goes through
+// K's vec_dot_type: f16 for F16, Q8_0 blocks for Q8_0 / Q4_0 / Q5_0, Q8_1 blocks for Q4_1 / Q5_1 -- quantize_row_q8_1: the same quants and d, and
+// s = f16(d * sum(qs)) with d not yet rounded; a block's score is (d_k * d_q) * sumi + m_k * s_q (ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1, ggml-cpu/quants.c:152-303): the
+// lanes add d_k n * d_q q element by element and the block's first lane adds m_k * s_q.  The instances of one type keep their arithmetic.
 #include "fattn_dev.hpp"
 
 namespace mi {
@@ -26,8 +31,30 @@ template <int T> static __device__ __forceinline__ float fa_any_elem(const char 
                                return h2f(*(const uint16_t *) b) * (float) ((int) (j < 16 ? by & 0xFu : by >> 4) - 8); }
 }
 
+// the same for a type known at run time (FA_ANY_MIXED): F16, Q8_0, Q4_0, Q4_1, Q5_0, Q5_1 (dequantize_row_q*, ggml-quants.c:307-398); with_min = false leaves a
+// Q4_1 / Q5_1 block's min out (K: the min goes against the query block's s)
+constexpr int FA_ANY_MIXED = -1;
+static __device__ __forceinline__ bool fa_any_has_min(int type) { return type == GGML_TYPE_Q4_1 || type == GGML_TYPE_Q5_1; }
+static __device__ __forceinline__ int  fa_any_block_bytes(int type) { return type == GGML_TYPE_Q8_0 ? 34 : type == GGML_TYPE_Q4_0 ? 18 : type == GGML_TYPE_Q4_1 ? 20 : type == GGML_TYPE_Q5_0 ? 22 : 24; }
+static __device__ __forceinline__ float fa_any_elem_rt(const int type, const char * row, const int d, const bool with_min) {
+    if (type == GGML_TYPE_F16) return h2f(((const uint16_t *) row)[d]);
+    const char * b = row + (d >> 5) * fa_any_block_bytes(type);
+    const int j = d & 31;
+    const float dd = h2f(*(const uint16_t *) b);
+    if (type == GGML_TYPE_Q8_0) return dd * (float) (int) (int8_t) b[2 + j];
+    const bool has_h = type == GGML_TYPE_Q5_0 || type == GGML_TYPE_Q5_1;
+    const int hoff = fa_any_has_min(type) ? 4 : 2, qoff = hoff + (has_h ? 4 : 0);
+    const uint32_t by = (uint8_t) b[qoff + (j & 15)];
+    int n = (int) (j < 16 ? by & 0xFu : by >> 4);
+    if (has_h) { const uint32_t qh = (uint32_t) *(const uint16_t *) (b + hoff) | ((uint32_t) *(const uint16_t *) (b + hoff + 2) << 16); n |= (int) ((qh >> j) & 1u) << 4; }
+    if (type == GGML_TYPE_Q4_0) n -= 8;
+    if (type == GGML_TYPE_Q5_0) n -= 16;
+    const float x = dd * (float) n;
+    return fa_any_has_min(type) && with_min ? x + h2f(*(const uint16_t *) (b + 2)) : x;
+}
+
 template <int NI, int T>
-__global__ void __launch_bounds__(256) k_fattn_any(const fa_dev a, const int Dk, const int Dv) {
+__global__ void __launch_bounds__(256) k_fattn_any(const fa_dev a, const int Dk, const int Dv, const int kt, const int vt) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= (int64_t) a.nq * a.nh * a.ns) return;
@@ -39,22 +66,31 @@ __global__ void __launch_bounds__(256) k_fattn_any(const fa_dev a, const int Dk,
     const char * kb = a.k + ikv * a.knb2 + is3 * a.knb3;
     const char * vb = a.v + ikv * a.vnb2 + is3 * a.vnb3;
     const uint16_t * mrow = a.mask ? (const uint16_t *) (a.mask + q * a.mnb1 + (h % (int) a.mne2) * a.mnb2 + (is3 % (int) a.mne3) * a.mnb3) : nullptr;
-    float qv[NI], o[NI];
+    const bool kmin = T == FA_ANY_MIXED && fa_any_has_min(kt);               // (uniform) Q8_1 query blocks
+    float qv[NI], qs[NI], o[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int d = lane + 64 * i;
         float x = d < Dk ? *(const float *) (qr + d * 4) : 0.0f;
-        if (T == GGML_TYPE_F16) x = h2f(f2h(x));
+        qs[i] = 0.0f;
+        if (T == GGML_TYPE_F16 || (T == FA_ANY_MIXED && kt == GGML_TYPE_F16)) x = h2f(f2h(x));
         else if (T == GGML_TYPE_BF16) {                                  // ggml_compute_fp32_to_bf16: round to nearest even (NaN kept quiet)
             uint32_t u = __float_as_uint(x);
             u = (u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) & 0xffff0000u : (u + (0x7fffu + ((u >> 16) & 1u))) & 0xffff0000u;
             x = __uint_as_float(u);
-        } else if (T == GGML_TYPE_Q8_0 || T == GGML_TYPE_Q4_0) {          // quantize_row_q8_0 on the 32-block the lane's element belongs to (a half wave)
+        } else if (T == GGML_TYPE_Q8_0 || T == GGML_TYPE_Q4_0 || T == FA_ANY_MIXED) {      // quantize_row_q8_0 on the 32-block the lane's element belongs to (a half wave)
             float amax = fabsf(x);
 #pragma unroll
             for (int off = 16; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
             const float dq = amax / 127.0f, id = amax != 0.0f ? 127.0f / amax : 0.0f;
-            x = h2f(f2h(dq)) * rintf(x * id);
+            const float qi = rintf(x * id);
+            if (kmin) {                                                  // block_q8_1.s, kept by the block's first lane
+                float sum = qi;
+#pragma unroll
+                for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                if ((d & 31) == 0) qs[i] = h2f(f2h(dq * sum));
+            }
+            x = h2f(f2h(dq)) * qi;
         }
         qv[i] = x;
         o[i] = 0.0f;
@@ -66,7 +102,13 @@ __global__ void __launch_bounds__(256) k_fattn_any(const fa_dev a, const int Dk,
         const char * kr = kb + (int64_t) kv * a.knb1;
         float part = 0.0f;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) { const int d = lane + 64 * i; if (d < Dk) part = fmaf(qv[i], fa_any_elem<T>(kr, d), part); }
+        for (int i = 0; i < NI; ++i) {
+            const int d = lane + 64 * i;
+            if (T == FA_ANY_MIXED) {
+                if (d < Dk) part = fmaf(qv[i], fa_any_elem_rt(kt, kr, d, false), part);
+                if (kmin && d < Dk && (d & 31) == 0) part = fmaf(qs[i], h2f(*(const uint16_t *) (kr + (d >> 5) * fa_any_block_bytes(kt) + 2)), part);
+            } else if (d < Dk) part = fmaf(qv[i], fa_any_elem<T>(kr, d), part);
+        }
         float s = wave_sum_f32(part) * a.scale;
         if (a.logit_softcap != 0.0f) s = a.logit_softcap * tanhf(s);
         s += mv;
@@ -74,7 +116,7 @@ __global__ void __launch_bounds__(256) k_fattn_any(const fa_dev a, const int Dk,
         if (s > M) { ms = expf(M - s); M = s; } else vs = expf(s - M);
         const char * vr = vb + (int64_t) kv * a.vnb1;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) { const int d = lane + 64 * i; if (d < Dv) o[i] = fmaf(vs, fa_any_elem<T>(vr, d), o[i] * ms); }
+        for (int i = 0; i < NI; ++i) { const int d = lane + 64 * i; if (d < Dv) o[i] = fmaf(vs, T == FA_ANY_MIXED ? fa_any_elem_rt(vt, vr, d, true) : fa_any_elem<T>(vr, d), o[i] * ms); }
         S = S * ms + vs;
     }
     if (a.sinks) {                                                       // ops.cpp:8116-8130
@@ -94,27 +136,33 @@ __global__ void __launch_bounds__(256) k_fattn_any(const fa_dev a, const int Dk,
 bool fattn_any_ok(int64_t Dk, int64_t Dv) { return Dk >= 1 && Dv >= 1 && Dk <= 64 * FA_ANY_MAXI && Dv <= 64 * FA_ANY_MAXI; }
 
 template <int T>
-static void fa_any_go(const fa_dev & a, int Dk, int Dv, hipStream_t st) {
+static void fa_any_go(const fa_dev & a, int Dk, int Dv, int kt, int vt, hipStream_t st) {
     const int64_t waves = (int64_t) a.nq * a.nh * a.ns;
     const dim3 grid((unsigned) ((waves + 3) / 4));
     const int ni = (int) (((Dk > Dv ? Dk : Dv) + 63) / 64);
     switch (ni) {
-        case 1: k_fattn_any<1, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv); break;
-        case 2: k_fattn_any<2, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv); break;
-        case 3: k_fattn_any<3, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv); break;
-        case 4: k_fattn_any<4, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv); break;
-        default: k_fattn_any<FA_ANY_MAXI, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv); break;
+        case 1: k_fattn_any<1, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv, kt, vt); break;
+        case 2: k_fattn_any<2, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv, kt, vt); break;
+        case 3: k_fattn_any<3, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv, kt, vt); break;
+        case 4: k_fattn_any<4, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv, kt, vt); break;
+        default: k_fattn_any<FA_ANY_MAXI, T><<<grid, dim3(256), 0, st>>>(a, Dk, Dv, kt, vt); break;
     }
 }
-void flash_attn_ext_any(const fa_dev & a, int Dk, int Dv, int kv_type, hipStream_t st) {
+void flash_attn_ext_any(const fa_dev & a, int Dk, int Dv, int k_type, int v_type, hipStream_t st) {
     if ((int64_t) a.nq * a.nh * a.ns == 0) return;
-    switch (kv_type) {
-        case GGML_TYPE_F16:  fa_any_go<GGML_TYPE_F16>(a, Dk, Dv, st); break;
-        case GGML_TYPE_F32:  fa_any_go<GGML_TYPE_F32>(a, Dk, Dv, st); break;
-        case GGML_TYPE_BF16: fa_any_go<GGML_TYPE_BF16>(a, Dk, Dv, st); break;
-        case GGML_TYPE_Q8_0: fa_any_go<GGML_TYPE_Q8_0>(a, Dk, Dv, st); break;
-        case GGML_TYPE_Q4_0: fa_any_go<GGML_TYPE_Q4_0>(a, Dk, Dv, st); break;
-        default: fprintf(stderr, "[mi355x] flash_attn: unsupported K / V type %d\n", kv_type); abort();
+    auto mixable = [](int t) { return t == GGML_TYPE_F16 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1; };
+    const bool one_type = k_type == v_type && (k_type == GGML_TYPE_F16 || k_type == GGML_TYPE_F32 || k_type == GGML_TYPE_BF16 || k_type == GGML_TYPE_Q8_0 || k_type == GGML_TYPE_Q4_0);
+    if (!one_type) {
+        if (!mixable(k_type) || !mixable(v_type)) { fprintf(stderr, "[mi355x] flash_attn: unsupported K / V types %d / %d\n", k_type, v_type); abort(); }
+        fa_any_go<FA_ANY_MIXED>(a, Dk, Dv, k_type, v_type, st);
+        return;
+    }
+    switch (k_type) {
+        case GGML_TYPE_F16:  fa_any_go<GGML_TYPE_F16>(a, Dk, Dv, k_type, v_type, st); break;
+        case GGML_TYPE_F32:  fa_any_go<GGML_TYPE_F32>(a, Dk, Dv, k_type, v_type, st); break;
+        case GGML_TYPE_BF16: fa_any_go<GGML_TYPE_BF16>(a, Dk, Dv, k_type, v_type, st); break;
+        case GGML_TYPE_Q8_0: fa_any_go<GGML_TYPE_Q8_0>(a, Dk, Dv, k_type, v_type, st); break;
+        default:             fa_any_go<GGML_TYPE_Q4_0>(a, Dk, Dv, k_type, v_type, st); break;
     }
 }
 

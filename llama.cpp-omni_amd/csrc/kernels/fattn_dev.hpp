@@ -47,7 +47,7 @@ void flash_attn_one(const fa_dev & a, int D, const float * rope_tab, hipStream_t
 void flash_attn_gs(const fa_dev & a, int D, const float * rope_tab, float * parts, hipStream_t st);
 // any other head size (fattn_any.hip): one wave per (query row, head, sequence)
 bool fattn_any_ok(int64_t Dk, int64_t Dv);
-void flash_attn_ext_any(const fa_dev & a, int Dk, int Dv, int kv_type, hipStream_t st);      // kv_type: F16 / F32 / BF16 / Q8_0 / Q4_0 (K and V alike)
+void flash_attn_ext_any(const fa_dev & a, int Dk, int Dv, int k_type, int v_type, hipStream_t st);      // F16 / F32 / BF16 / Q8_0 / Q4_0 (K and V alike), or K and V each one of F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1
 // head sizes 40, 72, 80, 96, 112, 256 (K and V alike), 192 / 128 and 576 / 512 over an F16 cache on the matrix cores (fattn_wide.hip; fattn_wide_dims is the list): 32-column tiles of (token, head) pairs as k_fattn_gqa, K / V tiles shared
 // through LDS by the waves of a workgroup, KV range in a.nsplit slices (-> a.part [column][slice][DV + 2] when > 1); fa_wide_plan (fattn.hip) decides
 bool fattn_wide_dims(int64_t Dk, int64_t Dv);
@@ -57,5 +57,9 @@ void flash_attn_ext_wide(const fa_dev & a, int Dk, int Dv, hipStream_t st);
 // slices and a.part as the wide kernel; fa_q_plan (fattn.hip) decides
 int  fattn_q_max_tiles();
 void flash_attn_ext_q(const fa_dev & a, int D, int kv_type, hipStream_t st);
+// head size 64 / 128 over K in Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 and V in one of those or F16, but for the two pairs above (fattn_qx.hip): K decoded to int8 rows + scale [+ min]
+// and V de-quantised to f32 rows while the tiles are staged, the query in Q8_1 form where K has a min; frame, slices and a.part as fattn_q.hip; fa_qx_plan (fattn.hip) decides
+int  fattn_qx_max_tiles();
+void flash_attn_ext_qx(const fa_dev & a, int D, int k_type, int v_type, hipStream_t st);
 
 } // namespace mi
