@@ -289,6 +289,13 @@ bool ssm_scan_ok(int64_t d_state, int64_t head_dim, int64_t n_head, int64_t n_gr
 void ssm_scan_f32(const tdesc & s, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const int * ids, float * dst, hipStream_t st);
 long ssm_conv_launches();
 long ssm_scan_launches();
+// SSM_SCAN over chunks of tokens on the f32 matrix cores (ssm_chunk.hip): Mamba-2 form (A {1, n_head}), head_dim a multiple of 32, d_state 64 / 128 / 256, from
+// ssm_chunk_min_tokens() tokens (128; MI355X_SSM_CHUNK_MIN_TOKENS raises it).  ssm_scan_f32 routes to it; such a launch counts in ssm_scan_launches() as well.
+void ssm_chunk_set_mode(int m);                // option "ssm_chunk": -1 = MI355X_SSM_CHUNK decides (default on), 0 off (k_ssm_scan at every token count: the cross-check switch), 1 on, 2 on at every token count (measurement)
+int  ssm_chunk_min_tokens();
+bool ssm_chunk_takes(int64_t A_ne0, int64_t d_state, int64_t head_dim, int64_t n_t);
+void ssm_scan_chunk_f32(const tdesc & s, const tdesc & x, const tdesc & dt, const tdesc & A, const tdesc & B, const tdesc & C, const int * ids, float * dst, hipStream_t st);
+long ssm_scan_chunk_launches();
 // RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM (wkv.hip; ops.cpp:9177, :9393, :9598, :3858), f32.  The WKV operands are contiguous {S, H, T} (tf {S, H}), the state source
 // n_seqs * S * S * H contiguous floats of any shape; dst {S * H, T + S * n_seqs}: the outputs, then the new states.  wkv_ok: the head sizes with a kernel (1 .. 128) and the launch
 // grid (heads and sequences <= 65535 each, T a multiple of n_seqs).  l2_norm: rows through nb1..nb3, nb[0] == 4.

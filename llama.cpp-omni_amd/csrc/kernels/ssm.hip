@@ -19,6 +19,7 @@
 //              (quad_perm, row_half_mirror, row_mirror) and, beyond a 16-lane row, one or two cross-lane swaps.  The decay is a template form: one exp per head
 //              and token (A {1, n_head}, Mamba-2) or one per state element and token (A {d_state, n_head}, Mamba-1; the four A values of a lane are loaded once).
 //              ids is read on the device: an input tensor that changes between replays of a captured graph.
+//              A Mamba-2 node of 128 tokens or more (ssm_chunk_takes) leaves for the chunked matrix-core kernel of ssm_chunk.hip.
 #include "../kernels.hpp"
 #include <type_traits>
 
@@ -253,6 +254,11 @@ void ssm_scan_f32(const tdesc & s, const tdesc & x, const tdesc & dt, const tdes
     const bool av = A.ne[0] != 1;
     if (!ssm_scan_ok(d_state, head_dim, n_head, n_group, n_t, n_s) || (av && A.ne[0] != d_state)) {
         fprintf(stderr, "[mi355x] ssm_scan_f32: d_state %lld, head_dim %lld, %lld heads, %lld groups, A->ne[0] %lld have no kernel\n", (long long) d_state, (long long) head_dim, (long long) n_head, (long long) n_group, (long long) A.ne[0]); abort();
+    }
+    if (ssm_chunk_takes(A.ne[0], d_state, head_dim, n_t)) {                     // a Mamba-2 prompt: chunks of tokens on the matrix cores (ssm_chunk.hip)
+        ssm_scan_chunk_f32(s, x, dt, A, B, C, ids, dst, st);
+        ++g_ssm_scan_launches;
+        return;
     }
     ssm_scan_args a;
     a.s = (const char *) s.p; a.s_nb3 = s.nb[3];

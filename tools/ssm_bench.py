@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""tools/ssm_bench.py -- SSM_SCAN and SSM_CONV (kernels/ssm.hip) at Mamba-2 2.7B shapes, timed as replayed captures through the backend C-ABI in the manner of
+"""tools/ssm_bench.py -- SSM_SCAN and SSM_CONV (kernels/ssm.hip, kernels/ssm_chunk.hip) at Mamba-2 2.7B shapes, timed as replayed captures through the backend C-ABI in the manner of
 tools/moe_mmv_bench.py: device time per launch, the launch's algorithmic bytes, and the fraction of 8 TB/s.
 
-  scan   d_state 128, head_dim 64, 80 heads, one group, at (n_t, n_s) = (1, 1), (1, 8), (1, 32), (512, 1).  Bytes: the states read once and written once (2 x 2.6 MB per
+  decode the scan, d_state 128, head_dim 64, 80 heads, one group, at (n_t, n_s) = (1, 1), (1, 8), (1, 32).  Bytes: the states read once and written once (2 x 2.6 MB per
          sequence), x, B, C and dt read, y written.
+  prompt the scan at 32 .. 2048 tokens, d_state 128 / 80 heads and d_state 256 / 32 heads, option "ssm_chunk" alternating in one call: 0 = the serial kernel k_ssm_scan,
+         2 = the chunked matrix-core kernel at every token count (its default threshold is 128 tokens; 32 and 64 are there to locate the crossover).  A library without
+         the option (an earlier build, through MI355X_LIB) runs the one leg it has.
   conv   5376 channels (d_inner 5120 + 2 x 128), d_conv 4, one sequence, at n_t = 1 and 512.  Bytes: the window tile read, y written, the weights.
 
 One cgraph holds N independent nodes, every node with its own operands (N x bytes > --min-mib MiB, default 768: the 256 MiB Infinity Cache cannot serve re-reads); it is
 run eager, captured, then replayed (at least 8 nodes: shorter graphs are never captured); the best of --reps replays is reported per node.  --rounds alternating rounds show the run-to-run spread.
 
-usage: python tools/ssm_bench.py [--reps 5] [--rounds 3] [--min-mib 768] > profiles/ssm_bench.txt
+usage: python tools/ssm_bench.py [--reps 5] [--rounds 3] [--min-mib 768] [--legs decode,prompt,conv] > profiles/ssm_bench.txt
 """
 import argparse
 import os
@@ -25,6 +28,7 @@ HBM = 8.0e12
 D_STATE, HEAD_DIM, N_HEAD, N_GROUP, D_CONV = 128, 64, 80, 1, 4
 D_INNER = HEAD_DIM * N_HEAD
 D_XBC = D_INNER + 2 * N_GROUP * D_STATE
+MAIN = (D_STATE, HEAD_DIM, N_HEAD, N_GROUP)
 
 
 def timed(be, g, reps):
@@ -41,48 +45,76 @@ def timed(be, g, reps):
     return best * 1e3
 
 
+def scan_leg(be, rng, args, label, shape, n_t, n_s, chunked=None):
+    from llama_cpp_omni_amd.ggml import Context
+    d_state, head_dim, n_head, n_group = shape
+    d_inner = head_dim * n_head
+    d_xbc = d_inner + 2 * n_group * d_state
+    state = d_state * d_inner * n_s * 4
+    node_bytes = 2 * state + (d_xbc + n_head) * n_t * n_s * 4 + d_inner * n_t * n_s * 4
+    n = max(8, min(256, (args.min_mib << 20) // node_bytes + 1))
+    c = Context(be)
+    A = c.new_tensor(F32, 1, n_head)
+    ids = c.new_tensor(I32, n_s)
+    ys, ins = [], []
+    for _ in range(n):
+        xBC = c.new_tensor(F32, d_xbc, n_t, n_s)
+        x = c.view_4d(xBC, head_dim, n_head, n_t, n_s, head_dim * 4, xBC.nb[1], xBC.nb[2], 0)
+        B = c.view_4d(xBC, d_state, n_group, n_t, n_s, d_state * 4, xBC.nb[1], xBC.nb[2], d_inner * 4)
+        C_ = c.view_4d(xBC, d_state, n_group, n_t, n_s, d_state * 4, xBC.nb[1], xBC.nb[2], (d_inner + n_group * d_state) * 4)
+        s = c.new_tensor(F32, d_state, head_dim, n_head, n_s)
+        dt = c.new_tensor(F32, n_head, n_t, n_s)
+        ys.append(c.ssm_scan(s, x, dt, A, B, C_, ids))
+        ins.append((xBC, s, dt))
+    assert be.supports_op(ys[0])
+    c.alloc()
+    be.tensor_set(A, -rng.uniform(0.05, 1.0, (n_head, 1)).astype(np.float32))
+    be.tensor_set(ids, np.arange(n_s, dtype=np.int32))
+    xv, sv, dv = (rng.standard_normal((n_s, n_t, d_xbc)).astype(np.float32), rng.standard_normal((n_s, n_head, head_dim, d_state)).astype(np.float32),
+                  rng.uniform(-2.0, 2.0, (n_s, n_t, n_head)).astype(np.float32))
+    for xBC, s, dt in ins:
+        be.tensor_set(xBC, xv); be.tensor_set(s, sv); be.tensor_set(dt, dv)
+    n0 = be.get_stat("ssm_scan_launches")
+    k0 = be.get_stat("ssm_scan_chunk_launches") if chunked is not None else 0
+    us = timed(be, c.graph(), args.reps) / n
+    d = be.get_stat("ssm_scan_launches") - n0
+    assert d in (0, 2 * n)                    # eager + capture, every node its own launch (0: a later round found its capture still cached and replayed at once)
+    if chunked is not None:
+        assert be.get_stat("ssm_scan_chunk_launches") - k0 == (d if chunked else 0)      # the leg ran the kernel it names
+    c.free()
+    print(f"{label} n_t={n_t:4d} n_s={n_s:2d}: {node_bytes / 1e6:6.1f} MB/launch  {us:8.2f} us ({node_bytes / us / 1e3:7.1f} GB/s, {node_bytes / us / 1e-6 / HBM:5.3f} of 8 TB/s, "
+          f"{n} nodes)  bytes / 8 TB/s {node_bytes / HBM * 1e6:6.2f} us", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--min-mib", type=int, default=768)
+    ap.add_argument("--legs", default="decode,prompt,conv")
     args = ap.parse_args()
     pkg = load_pkg()
     from llama_cpp_omni_amd.ggml import Context
     be = pkg.backend(0)
     rng = np.random.default_rng(0)
+    legs = args.legs.split(",")
     for rnd in range(args.rounds):
-        for n_t, n_s in [(1, 1), (1, 8), (1, 32), (512, 1)]:
-            state = D_STATE * D_INNER * n_s * 4
-            node_bytes = 2 * state + (D_XBC + N_HEAD) * n_t * n_s * 4 + D_INNER * n_t * n_s * 4
-            n = max(8, min(256, (args.min_mib << 20) // node_bytes + 1))
-            c = Context(be)
-            A = c.new_tensor(F32, 1, N_HEAD)
-            ids = c.new_tensor(I32, n_s)
-            ys, ins = [], []
-            for _ in range(n):
-                xBC = c.new_tensor(F32, D_XBC, n_t, n_s)
-                x = c.view_4d(xBC, HEAD_DIM, N_HEAD, n_t, n_s, HEAD_DIM * 4, xBC.nb[1], xBC.nb[2], 0)
-                B = c.view_4d(xBC, D_STATE, N_GROUP, n_t, n_s, D_STATE * 4, xBC.nb[1], xBC.nb[2], D_INNER * 4)
-                C_ = c.view_4d(xBC, D_STATE, N_GROUP, n_t, n_s, D_STATE * 4, xBC.nb[1], xBC.nb[2], (D_INNER + N_GROUP * D_STATE) * 4)
-                s = c.new_tensor(F32, D_STATE, HEAD_DIM, N_HEAD, n_s)
-                dt = c.new_tensor(F32, N_HEAD, n_t, n_s)
-                ys.append(c.ssm_scan(s, x, dt, A, B, C_, ids))
-                ins.append((xBC, s, dt))
-            assert be.supports_op(ys[0])
-            c.alloc()
-            be.tensor_set(A, -rng.uniform(0.05, 1.0, (N_HEAD, 1)).astype(np.float32))
-            be.tensor_set(ids, np.arange(n_s, dtype=np.int32))
-            xv, sv, dv = (rng.standard_normal((n_s, n_t, D_XBC)).astype(np.float32), rng.standard_normal((n_s, N_HEAD, HEAD_DIM, D_STATE)).astype(np.float32),
-                          rng.uniform(-2.0, 2.0, (n_s, n_t, N_HEAD)).astype(np.float32))
-            for xBC, s, dt in ins:
-                be.tensor_set(xBC, xv); be.tensor_set(s, sv); be.tensor_set(dt, dv)
-            n0 = be.get_stat("ssm_scan_launches")
-            us = timed(be, c.graph(), args.reps) / n
-            assert be.get_stat("ssm_scan_launches") - n0 in (0, 2 * n)  # eager + capture, every node its own launch (0: a later round found its capture still cached and replayed at once)
-            c.free()
-            print(f"round {rnd} ssm_scan n_t={n_t:3d} n_s={n_s:2d}: {node_bytes / 1e6:6.1f} MB/launch  {us:8.2f} us ({node_bytes / us / 1e3:7.1f} GB/s, {node_bytes / us / 1e-6 / HBM:5.3f} of 8 TB/s, "
-                  f"{n} nodes)  bytes / 8 TB/s {node_bytes / HBM * 1e6:6.2f} us", flush=True)
+        if "decode" in legs:
+            for n_t, n_s in [(1, 1), (1, 8), (1, 32)]:
+                scan_leg(be, rng, args, f"round {rnd} ssm_scan", MAIN, n_t, n_s)
+        if "prompt" in legs:
+            for shape, n_t, n_s in [(MAIN, 32, 1), (MAIN, 64, 1), (MAIN, 128, 1), (MAIN, 512, 1), (MAIN, 2048, 1), (MAIN, 512, 4), ((256, 64, 32, 1), 512, 1)]:
+                for mode, name in ((0, "serial "), (2, "chunked")):
+                    if be.set_option("ssm_chunk", mode) != 0:
+                        if mode == 0:
+                            scan_leg(be, rng, args, f"round {rnd} ssm_scan d_state={shape[0]} heads={shape[2]} no option", shape, n_t, n_s)
+                        continue
+                    try:
+                        scan_leg(be, rng, args, f"round {rnd} ssm_scan d_state={shape[0]} heads={shape[2]} {name}", shape, n_t, n_s, chunked=mode == 2)
+                    finally:
+                        be.set_option("ssm_chunk", -1)
+        if "conv" not in legs:
+            continue
         for n_t in (1, 512):
             node_bytes = (D_CONV - 1 + n_t) * D_XBC * 4 + n_t * D_XBC * 4 + D_CONV * D_XBC * 4
             n = max(8, min(256, (args.min_mib << 20) // node_bytes + 1))
