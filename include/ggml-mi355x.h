@@ -74,6 +74,10 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * "ssm_chunk" (-1 default (on) / 0 / 1 / 2: Mamba-2 SSM_SCAN nodes -- A {1, n_head}, head_dim a multiple of 32, d_state 64 / 128 / 256 -- of 128 tokens and more run over
  * chunks of tokens on the f32 matrix cores, csrc/kernels/ssm_chunk.hip; 0 keeps every node on the serial kernel: the cross-check switch; 2 takes such nodes at every token
  * count (measurement); process-wide, drops captured graphs; environment MI355X_SSM_CHUNK=0 is the default's off, MI355X_SSM_CHUNK_MIN_TOKENS=n raises the 128),
+ * "wkv_chunk" (-1 default (on) / 0 / 1 / 2: RWKV_WKV6 / GATED_LINEAR_ATTN nodes -- head size 64 / 128, 16-byte aligned operands, heads x sequences <= 256 resp. <= 64 -- of
+ * 64 tokens per sequence and more run over chunks of tokens on the f32 matrix cores, csrc/kernels/wkv_chunk.hip; 0 keeps every node on the serial kernels: the cross-check
+ * switch; 2 takes such nodes at every token count and grid (measurement, small test shapes); process-wide, drops captured graphs; environment MI355X_WKV_CHUNK=0 is the
+ * default's off, MI355X_WKV_CHUNK_MIN_TOKENS=n raises the 64),
  * "mv1", "mv2", "fattn_one", "kq_staging", "batch_uploads" (cross-check switches of the decode kernels),
  * "reset_stats".  Returns 0 on success, -1 for an unknown key.
  * Environment switches read once per process (measurement / cross-check only): MI355X_GRAPHS=0, MI355X_NO_CONV_FUSE, MI355X_NO_CONCAT_TAIL, MI355X_NO_ATTN_F32,
@@ -90,7 +94,8 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
  * integer mat-vec kernels of those weight types, up to 8 columns), "mmv_tq1_launches", "mmv_tq2_launches" (the same for TQ1_0 / TQ2_0), "mmq_tq_launches" (launches of the
  * ternary int8-MFMA kernel, one per 2-D slice of a node) and "mmq_tq_ks" (not a counter: the K split of the most recent one, 0 before the first), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
  * "argsort_launches", "ssm_conv_launches" / "ssm_scan_launches" (SSM_CONV / SSM_SCAN: one launch per node), "ssm_scan_chunk_launches" (those SSM_SCAN launches that ran the chunked kernel),
- * "wkv6_launches" / "gla_launches" / "wkv7_launches" / "l2_norm_launches" (RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM: one launch per node), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
+ * "wkv6_launches" / "gla_launches" / "wkv7_launches" / "l2_norm_launches" (RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM: one launch per node), "wkv6_chunk_launches" / "gla_chunk_launches" (those WKV6 / GLA launches that ran the chunked kernel)
+ * and "wkv_chunk_min_tokens" (not a counter: the token threshold in force), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
  * "mmq_id_launches" (MUL_MAT_ID nodes of K-quant experts that went through the expert-grouped launchers: the grouping and the matrix launch count as one, and such a
  * node does not touch "mmv_id_launches"), "mmq_id_mxfp4_launches" (the same for MXFP4 experts, counted apart; such a node does not touch "mmv_id_mxfp4_launches"),
  * "mmq_id_mxfp4_ks" (as "mmq_id_ks", for the most recent grouped MXFP4 launch),

@@ -308,6 +308,15 @@ void l2_norm_f32(const tdesc & x, const tdesc & y, float eps, hipStream_t st);
 long wkv6_launches();
 long gla_launches();
 long wkv7_launches();
+// RWKV_WKV6 / GATED_LINEAR_ATTN over chunks of tokens on the f32 matrix cores (wkv_chunk.hip): head size 64 / 128, 16-byte aligned operands, from wkv_chunk_min_tokens()
+// tokens per sequence (64; MI355X_WKV_CHUNK_MIN_TOKENS raises it), heads x sequences <= 256 (S = 64) / 64 (S = 128).  wkv6_f32 / gla_f32 route to it; such a launch counts in wkv6_launches() / gla_launches() as well.
+void wkv_chunk_set_mode(int m);                // option "wkv_chunk": -1 = MI355X_WKV_CHUNK decides (default on), 0 off (the serial kernels at every token count: the cross-check switch), 1 on, 2 on at every token count (measurement, small test shapes)
+int  wkv_chunk_min_tokens();
+bool wkv_chunk_takes(int64_t S, int64_t tokens_per_seq, bool aligned, int64_t head_seqs);      // head_seqs = heads x sequences: the grid must not exceed two rounds of workgroups (S = 64) / one (S = 128)
+void wkv6_chunk_f32(bool gla, const float * k, const float * v, const float * r, const float * tf, const float * d, const float * s_in, float * out, float * s_out, float scale,
+                    int64_t S, int64_t H, int64_t n_t, int64_t n_seqs, hipStream_t st);
+long wkv6_chunk_launches();
+long gla_chunk_launches();
 long l2_norm_launches();
 void conv_transpose_1d_f32(const tdesc & w, int w_type, const tdesc & x, const tdesc & y, int s0, hipStream_t st); // ops.cpp:5952-6122
 void cast_f32_i32(const tdesc & src, bool src_is_f32, const tdesc & dst, hipStream_t st);                          // ops.cpp:555, 558-561

@@ -23,6 +23,8 @@
 //   k_wkv6_any / k_wkv7_any   every other S from 1 to 128 (the loader probes with S = 123), or operands that are not 16-byte aligned: one workgroup per (head, sequence),
 //                        thread j owns column j (WKV6 / GLA: coalesced) or row i (WKV7) and keeps the state in dst between tokens -- the same thread writes and re-reads
 //                        an element.  Correct, not fast.
+//   A WKV6 / GLA node at S = 64 / 128 with aligned operands, wkv_chunk_min_tokens() tokens per sequence or more and few enough (head, sequence) pairs (wkv_chunk_takes)
+//   leaves for the chunked matrix-core kernel of wkv_chunk.hip; RWKV_WKV7 never does.
 #include "../kernels.hpp"
 #include <algorithm>
 
@@ -206,7 +208,9 @@ static void wkv_check(const char * what, int64_t S, int64_t H, int64_t T, int64_
 
 template <bool GLA>
 static void wkv6_go(wkv_args & a, int64_t S, int64_t H, int64_t T, int64_t n_seqs, hipStream_t st) {
-    if ((S == 64 || S == 128) && wkv_aligned(a)) {
+    if (wkv_chunk_takes(S, T / n_seqs, wkv_aligned(a), H * n_seqs))                 // a prompt: chunks of tokens on the matrix cores (wkv_chunk.hip)
+        wkv6_chunk_f32(GLA, a.p[0], a.p[1], a.p[2], a.p[3], a.p[4], a.s_in, a.out, a.s_out, a.scale, S, H, T / n_seqs, n_seqs, st);
+    else if ((S == 64 || S == 128) && wkv_aligned(a)) {
         const bool narrow = H * n_seqs * (S / 16) < 512;             // 8 columns per wave while 16 leave fewer than 512 waves
         const dim3 grid((unsigned) (S / (narrow ? 8 : 16)), (unsigned) H, (unsigned) n_seqs);
         if (S == 64) { if (narrow) k_wkv6<64, 8, GLA><<<grid, dim3(64), 0, st>>>(a);  else k_wkv6<64, 16, GLA><<<grid, dim3(64), 0, st>>>(a); }
