@@ -77,7 +77,8 @@ GGML_MI355X_API void   mi355x_timed_event_free(void * ev);
  * "wkv_chunk" (-1 default (on) / 0 / 1 / 2: RWKV_WKV6 / GATED_LINEAR_ATTN nodes -- head size 64 / 128, 16-byte aligned operands, heads x sequences <= 256 resp. <= 64 -- of
  * 64 tokens per sequence and more run over chunks of tokens on the f32 matrix cores, csrc/kernels/wkv_chunk.hip; 0 keeps every node on the serial kernels: the cross-check
  * switch; 2 takes such nodes at every token count and grid (measurement, small test shapes); process-wide, drops captured graphs; environment MI355X_WKV_CHUNK=0 is the
- * default's off, MI355X_WKV_CHUNK_MIN_TOKENS=n raises the 64),
+ * default's off, MI355X_WKV_CHUNK_MIN_TOKENS=n raises the 64; the option governs RWKV_WKV7 nodes as well -- the same head sizes and alignment, 64 tokens per sequence and
+ * more (the same environment variable raises it), heads x sequences <= 256 resp. <= 128 -- which run on csrc/kernels/wkv7_chunk.hip; 0 keeps them on the serial kernels too),
  * "mv1", "mv2", "fattn_one", "kq_staging", "batch_uploads" (cross-check switches of the decode kernels),
  * "reset_stats".  Returns 0 on success, -1 for an unknown key.
  * Environment switches read once per process (measurement / cross-check only): MI355X_GRAPHS=0, MI355X_NO_CONV_FUSE, MI355X_NO_CONCAT_TAIL, MI355X_NO_ATTN_F32,
@@ -95,7 +96,7 @@ GGML_MI355X_API int    mi355x_set_option(struct ggml_backend * backend, const ch
  * ternary int8-MFMA kernel, one per 2-D slice of a node) and "mmq_tq_ks" (not a counter: the K split of the most recent one, 0 before the first), "mmv_id_launches" (MUL_MAT_ID launches: one covers every (slot, token) pair of a node),
  * "argsort_launches", "ssm_conv_launches" / "ssm_scan_launches" (SSM_CONV / SSM_SCAN: one launch per node), "ssm_scan_chunk_launches" (those SSM_SCAN launches that ran the chunked kernel),
  * "wkv6_launches" / "gla_launches" / "wkv7_launches" / "l2_norm_launches" (RWKV_WKV6 / GATED_LINEAR_ATTN / RWKV_WKV7 / L2_NORM: one launch per node), "wkv6_chunk_launches" / "gla_chunk_launches" (those WKV6 / GLA launches that ran the chunked kernel)
- * and "wkv_chunk_min_tokens" (not a counter: the token threshold in force), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
+ * and "wkv_chunk_min_tokens" (not a counter: the token threshold in force), "wkv7_chunk_launches" (those WKV7 launches that ran the chunked kernel) and "wkv7_chunk_min_tokens" (not a counter: its threshold in force), "mmv_id_mxfp4_launches" (MUL_MAT_ID launches on MXFP4 experts, counted apart from "mmv_id_launches"), "add_id_launches" (ADD_ID: one launch per node),
  * "mmq_id_launches" (MUL_MAT_ID nodes of K-quant experts that went through the expert-grouped launchers: the grouping and the matrix launch count as one, and such a
  * node does not touch "mmv_id_launches"), "mmq_id_mxfp4_launches" (the same for MXFP4 experts, counted apart; such a node does not touch "mmv_id_mxfp4_launches"),
  * "mmq_id_mxfp4_ks" (as "mmq_id_ks", for the most recent grouped MXFP4 launch),

@@ -389,7 +389,7 @@ int mi355x_set_option(struct ggml_backend * backend, const char * key, long valu
     if (!strcmp(key, "fattn_q")) { mi::fattn_set_q((int) value); mi::drop_graph_execs(c); return 0; }          // (process-wide)
     if (!strcmp(key, "fattn_qx")) { mi::fattn_set_qx((int) value); mi::drop_graph_execs(c); return 0; }        // (process-wide)
     if (!strcmp(key, "ssm_chunk")) { mi::ssm_chunk_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: Mamba-2 SSM_SCAN nodes from 128 tokens on the chunked f32-MFMA kernel of ssm_chunk.hip; 0 = k_ssm_scan at every token count: the cross-check switch; 2 = at every token count: measurement)
-    if (!strcmp(key, "wkv_chunk")) { mi::wkv_chunk_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: RWKV_WKV6 / GATED_LINEAR_ATTN nodes at head size 64 / 128 from wkv_chunk_min_tokens() tokens per sequence on the chunked f32-MFMA kernel of wkv_chunk.hip; 0 = the serial kernels at every token count: the cross-check switch; 2 = at every token count: measurement)
+    if (!strcmp(key, "wkv_chunk")) { mi::wkv_chunk_set_mode((int) value); mi::drop_graph_execs(c); return 0; }      // (process-wide: RWKV_WKV6 / GATED_LINEAR_ATTN nodes at head size 64 / 128 from wkv_chunk_min_tokens() tokens per sequence on the chunked f32-MFMA kernel of wkv_chunk.hip; 0 = the serial kernels at every token count: the cross-check switch; 2 = at every token count: measurement; RWKV_WKV7 nodes follow the same option onto wkv7_chunk.hip)
     if (!strcmp(key, "f16_shadow")) { mi::shadow_set_enabled(value != 0); mi::drop_graph_execs(c); return 0; }
     if (!strcmp(key, "reset_stats")) { c->prof.clear(); c->stat_replays = c->stat_captures = c->stat_eager = 0; return 0; }
     return -1;
@@ -449,6 +449,8 @@ double mi355x_get_stat(struct ggml_backend * backend, const char * key) {
     if (!strcmp(key, "wkv6_chunk_launches")) return (double) mi::wkv6_chunk_launches();
     if (!strcmp(key, "gla_chunk_launches"))  return (double) mi::gla_chunk_launches();
     if (!strcmp(key, "wkv_chunk_min_tokens")) return (double) mi::wkv_chunk_min_tokens();      // (not a counter: the threshold in force)
+    if (!strcmp(key, "wkv7_chunk_launches")) return (double) mi::wkv7_chunk_launches();
+    if (!strcmp(key, "wkv7_chunk_min_tokens")) return (double) mi::wkv7_chunk_min_tokens();    // (not a counter: the threshold in force)
     if (!strcmp(key, "wkv7_launches"))      return (double) mi::wkv7_launches();
     if (!strcmp(key, "l2_norm_launches"))   return (double) mi::l2_norm_launches();
     if (!strcmp(key, "mmv_id_mxfp4_launches")) return (double) mi::mmv_id_mxfp4_launches();

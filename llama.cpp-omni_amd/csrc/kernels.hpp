@@ -317,6 +317,14 @@ void wkv6_chunk_f32(bool gla, const float * k, const float * v, const float * r,
                     int64_t S, int64_t H, int64_t n_t, int64_t n_seqs, hipStream_t st);
 long wkv6_chunk_launches();
 long gla_chunk_launches();
+int  wkv_chunk_mode();                         // the option and MI355X_WKV_CHUNK folded: 0 off, 1 by threshold, 2 at every token count and grid
+// RWKV_WKV7 over chunks of tokens on the f32 matrix cores (wkv7_chunk.hip), under the same option: head size 64 / 128, 16-byte aligned operands, from wkv7_chunk_min_tokens()
+// tokens per sequence (64; MI355X_WKV_CHUNK_MIN_TOKENS raises it), at most 512 workgroups (heads x sequences x S / 32).  wkv7_f32 routes to it; such a launch counts in wkv7_launches() as well.
+int  wkv7_chunk_min_tokens();
+bool wkv7_chunk_takes(int64_t S, int64_t tokens_per_seq, bool aligned, int64_t head_seqs);
+void wkv7_chunk_f32(const float * r, const float * w, const float * k, const float * v, const float * a, const float * b, const float * s_in, float * out, float * s_out,
+                    int64_t S, int64_t H, int64_t n_t, int64_t n_seqs, hipStream_t st);
+long wkv7_chunk_launches();
 long l2_norm_launches();
 void conv_transpose_1d_f32(const tdesc & w, int w_type, const tdesc & x, const tdesc & y, int s0, hipStream_t st); // ops.cpp:5952-6122
 void cast_f32_i32(const tdesc & src, bool src_is_f32, const tdesc & dst, hipStream_t st);                          // ops.cpp:555, 558-561

@@ -24,7 +24,7 @@
 //                        thread j owns column j (WKV6 / GLA: coalesced) or row i (WKV7) and keeps the state in dst between tokens -- the same thread writes and re-reads
 //                        an element.  Correct, not fast.
 //   A WKV6 / GLA node at S = 64 / 128 with aligned operands, wkv_chunk_min_tokens() tokens per sequence or more and few enough (head, sequence) pairs (wkv_chunk_takes)
-//   leaves for the chunked matrix-core kernel of wkv_chunk.hip; RWKV_WKV7 never does.
+//   leaves for the chunked matrix-core kernel of wkv_chunk.hip; a RWKV_WKV7 node that wkv7_chunk_takes admits leaves for wkv7_chunk.hip's.
 #include "../kernels.hpp"
 #include <algorithm>
 
@@ -236,7 +236,9 @@ void gla_f32(const float * k, const float * v, const float * q, const float * g,
 void wkv7_f32(const float * r, const float * w, const float * k, const float * v, const float * av, const float * b, const float * state, float * dst, int64_t S, int64_t H, int64_t T, int64_t n_seqs, hipStream_t st) {
     wkv_check("wkv7_f32", S, H, T, n_seqs);
     wkv_args a = { { r, w, k, v, av, b }, state, dst, dst + (size_t) S * H * T, 0.0f, (int) H, (int) (T / n_seqs) };
-    if ((S == 64 || S == 128) && wkv_aligned(a)) {
+    if (wkv7_chunk_takes(S, T / n_seqs, wkv_aligned(a), H * n_seqs))                // a prompt: chunks of tokens on the matrix cores (wkv7_chunk.hip)
+        wkv7_chunk_f32(r, w, k, v, av, b, a.s_in, a.out, a.s_out, S, H, T / n_seqs, n_seqs, st);
+    else if ((S == 64 || S == 128) && wkv_aligned(a)) {
         const dim3 grid((unsigned) (S / 8), (unsigned) H, (unsigned) n_seqs);
         if (S == 64) k_wkv7<64, 8><<<grid, dim3(64), 0, st>>>(a); else k_wkv7<128, 8><<<grid, dim3(64), 0, st>>>(a);
     } else

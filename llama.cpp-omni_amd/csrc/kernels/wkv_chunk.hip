@@ -3,7 +3,8 @@
 // What it takes (wkv_chunk_takes): head size 64 or 128, 16-byte aligned operands, at least wkv_chunk_min_tokens() tokens per sequence (64; MI355X_WKV_CHUNK_MIN_TOKENS
 // raises it), and a grid of at most 512 workgroups at S = 64 (heads x sequences <= 256) resp. 256 at S = 128 (<= 64): beyond that the latency-bound serial kernel, to
 // which further sequences come free, is the faster one (measured).  Everything else -- other head sizes, unaligned operands, shorter ubatches and decode, many
-// sequences, option "wkv_chunk" = 0, RWKV_WKV7 -- stays on the serial kernels of wkv.hip.  wkv6_go (wkv.hip) routes; a node is one launch either way.
+// sequences, option "wkv_chunk" = 0 -- stays on the serial kernels of wkv.hip.  wkv6_go (wkv.hip) routes; a node is one launch either way.  RWKV_WKV7 has a chunked
+// kernel of its own, wkv7_chunk.hip, under the same option.
 //
 // The mathematics (ggml_compute_forward_rwkv_wkv6_f32 / _gla_f32 restated; layouts as in wkv.hip's header), per (sequence, head): state s[i][j], i the k index, j the v
 // index, decay d_t[i] per CHANNEL and token (td / g).  A decay travels as l = max(logf(|d|), -128) and sg = sign(d) (+1 for 0); products of decays are sums of l and
@@ -337,11 +338,15 @@ int wkv_chunk_min_tokens() {
     return v;
 }
 
-bool wkv_chunk_takes(int64_t S, int64_t tokens_per_seq, bool aligned, int64_t head_seqs) {
+int wkv_chunk_mode() {                       // the option and MI355X_WKV_CHUNK folded: 0 off, 1 by threshold, 2 every token count and grid
     static const bool env_on = [] { const char * e = getenv("MI355X_WKV_CHUNK"); return !e || atoi(e) != 0; }();
-    if (g_wkv_chunk_mode == 0 || (g_wkv_chunk_mode < 0 && !env_on)) return false;
-    if ((S != 64 && S != 128) || !aligned) return false;
-    if (g_wkv_chunk_mode == 2) return tokens_per_seq >= 1;       // 2: every token count and grid (tools/wkv_bench.py locates the crossovers with it)
+    return g_wkv_chunk_mode == 0 || (g_wkv_chunk_mode < 0 && !env_on) ? 0 : g_wkv_chunk_mode == 2 ? 2 : 1;
+}
+
+bool wkv_chunk_takes(int64_t S, int64_t tokens_per_seq, bool aligned, int64_t head_seqs) {
+    const int mode = wkv_chunk_mode();
+    if (mode == 0 || (S != 64 && S != 128) || !aligned) return false;
+    if (mode == 2) return tokens_per_seq >= 1;       // 2: every token count and grid (tools/wkv_bench.py locates the crossovers with it)
     // the serial kernel is latency-bound: further sequences cost it nothing until the machine is full, while this kernel's time multiplies with every round of 256
     // workgroups.  Measured (profiles/wkv_chunk_bench.txt): two rounds still win at S = 64, at S = 128 only one does.
     return tokens_per_seq >= wkv_chunk_min_tokens() && head_seqs * (S / 32) <= (S == 64 ? 2 : 1) * WKV_CHUNK_CUS;

@@ -7,6 +7,8 @@ the operands read, the outputs written) and, for the decode cases, the fraction 
   prompt WKV6 and GLA at 16 .. 2048 tokens of one sequence, 64 .. 512 tokens of 4 and 8 sequences, and 32 heads of 128 at 1 / 2 / 4 sequences, option "wkv_chunk" alternating in one call: 0 = the serial kernel k_wkv6,
          2 = the chunked matrix-core kernel at every token count and grid (the short and the many-sequence ones are there to locate the crossovers); WKV7, which has no chunked kernel, at 512 tokens.  A
          library without the option (an earlier build, through MI355X_LIB) runs the one leg it has.
+  prompt7 WKV7 (kernels/wkv7_chunk.hip) at 16 .. 2048 tokens of one sequence and 64 .. 512 of 4 and 8, 64 heads of 64 and 32 heads of 128, the option alternating the same way: 0 = k_wkv7,
+         2 = k_wkv7_chunk.  A build from before that kernel runs k_wkv7 alone.
 
 One cgraph holds N independent nodes, every node with its own operands (N x bytes > --min-mib MiB, default 768: the 256 MiB Infinity Cache cannot serve re-reads); it is
 run eager, captured, then replayed (at least 8 nodes); the best of --reps replays is reported per node.  --rounds alternating rounds show the run-to-run spread.
@@ -25,6 +27,7 @@ from bench import load_pkg  # noqa: E402
 F32 = 0
 HBM = 8.0e12
 MAIN = (64, 64)                                          # (head size, heads)
+WIDE = (128, 32)
 N_OPERANDS = {"wkv6": 4, "gla": 4, "wkv7": 6}           # {S, H, T} operands read per token
 
 
@@ -69,7 +72,7 @@ def leg(be, rng, args, label, op, shape, n_t, n_s, chunked=None):
     sv = rng.standard_normal((n_s, S * S * H)).astype(np.float32)
     for t3, st in ins:
         for i, t in enumerate(t3):
-            be.tensor_set(t, decay if i == 3 and op != "wkv7" else small)
+            be.tensor_set(t, decay if i == (1 if op == "wkv7" else 3) else small)      # (WKV7: r w k v a b)
         be.tensor_set(st, sv)
     key = f"{op}_chunk_launches"
     k0 = be.get_stat(key) if chunked is not None else 0
@@ -99,6 +102,16 @@ def main():
             for op in ("wkv6", "gla", "wkv7"):
                 for n_s in (1, 8, 32):
                     leg(be, rng, args, f"round {rnd} decode        ", op, MAIN, 1, n_s)
+        if "prompt7" in legs:
+            has7 = be.get_stat("wkv7_chunk_min_tokens") > 0                  # (a build from before wkv7_chunk.hip: the one kernel it has)
+            for shape, n_t, n_s in ([(MAIN, t, 1) for t in (16, 32, 48, 64, 96, 128, 256, 512, 2048)] + [(MAIN, t, n) for n in (4, 8) for t in (64, 128, 512)]
+                                    + [(WIDE, t, 1) for t in (32, 64, 128, 512, 2048)] + [(WIDE, t, n) for n in (4, 8) for t in (64, 512)]):
+                for mode, name in ((0, "serial "), (2, "chunked")) if has7 else ((-1, "no kern."),):
+                    be.set_option("wkv_chunk", mode)
+                    try:
+                        leg(be, rng, args, f"round {rnd} prompt {name}", "wkv7", shape, n_t, n_s, chunked=mode == 2 if has7 else None)
+                    finally:
+                        be.set_option("wkv_chunk", -1)
         if "prompt" not in legs:
             continue
         leg(be, rng, args, f"round {rnd} prompt        ", "wkv7", MAIN, 512, 1)
